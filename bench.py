@@ -2,11 +2,17 @@
 12+12 layers, d_model 512, h 8, ff 2048, batch 64 per GPU, T=1000 frames of 80-bin log-mel, L=64 tokens,
 bf16, dropout 0.1, fused AdamW), data-parallel over N GPUs (weak scaling: 64 utterances per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0). `value` = all ranks' frames / max-over-ranks wall time of the K timed steps.
+Prints ONE JSON line (rank 0). `value` = all ranks' frames / max-over-ranks wall time of the K timed steps;
+`ms_per_step` = that wall time / K.  A plain run does only that: set up, warm up, time the K steps.
+`--dump-outputs DIR` then writes what the last timed step left its caller (DIR/<name>.npy, float32: the loss, and
+a fixed seeded sample of the updated fp32 master weights and of the gradients); the inputs are the same from run
+to run, so two builds can be compared array for array.
+
+`--full` adds the supplementary measurements (each can be switched off again with its `--no-*` option):
 `roofline` = the dominant GEMM kernel instantiation (largest total time in the last warmup step, named as
 rocprofv3 names it), timed live with HIP events on its launch stream over the timed steps; `sub_rooflines` = the
 north_star's per-kernel figures (attention projection GEMM and fused attention: MFMA fraction; LayerNorm and the
@@ -39,6 +45,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel probe (roofline), sub-rooflines, the c2 / c5 / new_small configs and the "
+                         "CPU baseline; the --no-* options below switch parts of it off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=4)
@@ -47,7 +58,10 @@ def parse():
     ap.add_argument("--no-sub", action="store_true", help="skip the per-kernel sub-rooflines")
     ap.add_argument("--no-other", action="store_true", help="skip the c2 / c5 forward configs")
     ap.add_argument("--cpu-dist-selftest", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:   # a plain run measures the headline only
+        args.no_probe = args.no_sub = args.no_other = args.no_cpu_baseline = True
+    return args
 
 
 def host_cpu():
@@ -452,6 +466,24 @@ def other_configs(names=("c2", "c5"), reps=5):
     return out
 
 
+DUMP_SAMPLE = 1 << 22    # elements of each flat buffer written by --dump-outputs (16 MiB as float32)
+
+
+def dump_outputs(path, trainer, loss):
+    """`--dump-outputs`: what the last timed step left its caller, as float32 .npy files under `path`: the loss it
+    returned (`loss`), and the fp32 master weights it updated and the gradients it computed (`params_sample`,
+    `grads_sample`: the same DUMP_SAMPLE positions of both flat buffers, drawn from a fixed seed)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat, grad = trainer.store.flat, trainer.store.grad
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(0).integers(0, n, size=min(n, DUMP_SAMPLE)))
+    sel = torch.from_numpy(idx).to(flat.device)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), flat.detach()[sel].float().cpu().numpy())
+    np.save(os.path.join(path, "grads_sample.npy"), grad.detach()[sel].float().cpu().numpy())
+
+
 def _free_port():
     import socket
     so = socket.socket()
@@ -584,6 +616,8 @@ def main():
         dist.barrier()
     dt = time.perf_counter() - t0
     K.PROBE = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
     if dp:
         x = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(x, op=dist.ReduceOp.MAX)

@@ -21,6 +21,7 @@ from modules.Transformer.layers import TrainablePositionalEncoding  # noqa: E402
 from modules.Transformer.model import Transformer  # noqa: E402
 
 from oracle.ref_model import CONFIGS, det_params, synthetic_batch  # noqa: E402
+from tests.golden_io import save_golden  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -119,7 +120,7 @@ def gen_model(name, train_grads_full):
     out["greedy_nprobs"] = np.int64(len(probs))
     if len(probs):
         out["greedy_last_probs"] = np32(probs[-1])
-    np.savez_compressed(os.path.join(OUT, f"model_{name}.npz"), **out)
+    save_golden(os.path.join(OUT, f"model_{name}.npz"), out)
 
 
 def gen_grads(name, full_filter=None):
@@ -147,7 +148,7 @@ def gen_grads(name, full_filter=None):
     out["grad_names"] = np.array(names)
     out["grad_norms"] = np.array(norms, dtype=np.float64)
     out["nograd_names"] = np.array([k for k, p in mt.named_parameters() if p.grad is None])
-    np.savez_compressed(os.path.join(OUT, f"grads_{name}.npz"), **out)
+    save_golden(os.path.join(OUT, f"grads_{name}.npz"), out)
 
 
 def gen_schema():

@@ -30,6 +30,7 @@ sys.modules["modules.Transformer.masking"] = _nm
 _model = importlib.import_module("modules.Transformer.new.model")
 
 from oracle.ref_model_new import NEW_CONFIGS, det_params, synthetic_batch  # noqa: E402
+from tests.golden_io import save_golden  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -94,7 +95,7 @@ def main():
         out[p + "eval_tokens"], out[p + "eval_last"], out[p + "eval_eoses"] = \
             preds.numpy(), np32(last), eoses.numpy()
         print(name, "loss", float(loss), "logits", tuple(logits.shape), "tokens", preds[0].tolist())
-    np.savez_compressed(os.path.join(OUT, "new_model.npz"), **out)
+    save_golden(os.path.join(OUT, "new_model.npz"), out)
     with open(os.path.join(OUT, "ref_new_state_dict_schema.json"), "w") as f:
         json.dump(schema, f)
 

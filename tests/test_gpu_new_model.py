@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import ref_model_new as N
+from tests.golden_io import load_golden
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -42,7 +43,7 @@ def build(name, precision="fp32", dropout=None, seed=0):
 
 
 def golden_batch(golden_dir, name):
-    g = np.load(os.path.join(golden_dir, "new_model.npz"))
+    g = load_golden(golden_dir, "new_model.npz")
     p = name + "/"
     batch = {"spectre": torch.from_numpy(g[p + "spectre"]).to(dev),
              "spectrogram_len": torch.from_numpy(g[p + "lens"]).to(dev),

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from oracle.ref_model import CONFIGS, det_params, synthetic_batch, train_step_grads
+from tests.golden_io import load_golden
 
 pytestmark = pytest.mark.gpu
 dev = "cuda"
@@ -116,7 +117,7 @@ def check_grads(gsd, ref, names, label, ref_bf16=None):
 def test_trainer_grads_vs_reference_golden(golden_dir, name):
     """g64: T' = 49 -> resident-K/V attention kernels; g64l: T' = 274 -> tiled attention kernels (encoder self and
     cross attention).  Full gradient tensors from the reference itself (norms where the fixture holds only those)."""
-    g = np.load(os.path.join(golden_dir, f"grads_{name}.npz"))
+    g = load_golden(golden_dir, f"grads_{name}.npz")
     m, cfg = build(name)
     s, t, k = (torch.from_numpy(g[x]).to(dev) for x in ("spectrum", "text", "mask"))
     loss, _ = trainer_grads(m, s, t, k)

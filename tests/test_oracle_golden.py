@@ -5,13 +5,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests.golden_io import load_golden
 from oracle.ref_model import (CONFIGS, attention_head, decoder_layer, decoder_mask, det_params, encoder, feed_forward,
                               forward, front_end, greedy_decode, multi_head, pe_table, synthetic_batch,
                               train_step_grads, _ln)
 
 
 def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name))
+    return load_golden(golden_dir, name)
 
 
 def rel(a, b):

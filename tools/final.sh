@@ -21,7 +21,7 @@ step pmctr 120 python3 tools/pmc_traffic.py gpurun_out/pmcf/run_counter_collecti
 step pmcm 300 timeout -s KILL 240 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d gpurun_out/pmcm -o run --output-format csv -- $B
 step pmcmj 120 python3 tools/pmc_mfma.py gpurun_out/pmcm/run_counter_collection.csv --out gpurun_out/c3_pmc_mfma.json
 cp gpurun_out/c3_pmc_traffic.json gpurun_out/c3_pmc_mfma.json profiles/   # (the bench line below reads them)
-step bench 900 python bench.py
+step bench 900 python bench.py --full
 step prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline --no-probe --no-sub --no-other
 step steptab 120 python3 tools/step_table.py gpurun_out/prof/run_kernel_trace.csv
 if [ $# -gt 0 ]; then bash tools/prof_step.sh fin ASRX_NONE=0 "$@" || exit $?; fi

@@ -13,5 +13,5 @@ step pmctr 120 python3 tools/pmc_traffic.py gpurun_out/pmcf/run_counter_collecti
 step pmcm 200 timeout -s KILL 180 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d gpurun_out/pmcm -o run --output-format csv -- $B
 step pmcmj 120 python3 tools/pmc_mfma.py gpurun_out/pmcm/run_counter_collection.csv --out gpurun_out/c3_pmc_mfma.json
 cp gpurun_out/c3_pmc_traffic.json gpurun_out/c3_pmc_mfma.json profiles/
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 cat gpurun_out/bench.log | grep '^{' > gpurun_out/bench_line.json

@@ -27,8 +27,8 @@ for step in "$@"; do
     model)   run model 1200 python -m pytest tests/test_gpu_model.py -q -m gpu -rf --timeout=600 ;;
     gpu)     run gputests 1500 python -m pytest tests -q -m gpu -rf --timeout=600 ;;
     smoke)   run smoke 300 python __graft_entry__.py smoke ;;
-    bench)   run bench 900 python bench.py --steps 10 --warmup 3 ;;
-    benchq)  run benchq 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench)   run bench 900 python bench.py --full --steps 10 --warmup 3 ;;
+    benchq)  run benchq 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
     prof)    run prof 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-probe --no-sub --no-other ;;
     pmcf)    run pmcf 900 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmcf -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-probe --no-sub --no-other ;;
     pmcw)    run pmcw 900 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmcw -o run --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-probe --no-sub --no-other ;;
