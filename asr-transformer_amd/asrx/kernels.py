@@ -870,9 +870,12 @@ def embed_bwd(tok, dout, dtable, L, pad_id, dropout_p=0.0, seed=0):
 
 
 def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_grad=True, want_argmax=False):
-    """logits fp32 [rows, ld]; returns (loss[1], dlogits bf16 [rows, ld] or None, argmax or None)."""
+    """logits fp32 [rows, ld], rows contiguous (the kernel writes dlogits with the logits' row stride, so a
+    row-strided view is refused); returns (loss[1], dlogits bf16 [rows, ld] or None, argmax or None)."""
     _cuda(logits, target)
     rows, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
+        "asrx: cross_entropy needs contiguous fp32 logits [rows, ld]"
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
     dl = torch.empty(rows, ld, device=logits.device, dtype=torch.bfloat16) if want_grad else None
     am = torch.empty(rows, device=logits.device, dtype=torch.int64) if want_argmax else None
@@ -908,7 +911,8 @@ def adam_desc(p, m, v, p_bf16, g, lr, beta1, beta2, eps, weight_decay, step, gra
 
 def adam_spans(p, g, m, v, p_bf16, spans, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, decoupled=False,
                hyp=None):
-    """AdamW over the element ranges of a device int64 [n, 2] table (bounds multiples of 4; asrx_adam_spans)."""
+    """AdamW over the element ranges of a device int64 [n, 2] table (asrx_adam_spans; any bounds: a bound that
+    is not a multiple of 4 gets its head / tail elements stepped one at a time, empty ranges are skipped)."""
     _cuda(p, g, m, v, p_bf16, spans, hyp)
     call("asrx_adam_spans", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p_bf16), spans.data_ptr(),
          spans.shape[0], lr, beta1, beta2, eps, weight_decay, 1.0 - beta1 ** step, 1.0 - beta2 ** step, grad_scale,

@@ -350,10 +350,20 @@ __global__ __launch_bounds__(256) void reduce_rows_grouped_kernel(RowsumTable t)
   }
 }
 
+// load_ch / store_ch move CH elements per access (16 B of fp32, 8 B of bf16 at CH = 4): a pointer that is not
+// aligned to that width (a view into a larger buffer) takes the any-width kernels' element accesses instead.
+template <int CH>
+bool ln_aligned(const void* p, int dtype) {
+  return (uintptr_t)p % (CH * (dtype == ASRX_F32 ? 4 : 2)) == 0;
+}
+
 template <int CH, int NJ>
 bool ln_fwd_launch(int x_dtype, const void* x, int y_dtype, void* y, const float* gamma, const float* beta,
                    float* mean, float* rstd, int64_t rows, int d, float eps, hipStream_t st) {
   if (d != CH * NJ * 64) return false;
+  if (!ln_aligned<CH>(x, x_dtype) || !ln_aligned<CH>(y, y_dtype) || !ln_aligned<CH>(gamma, ASRX_F32) ||
+      !ln_aligned<CH>(beta, ASRX_F32))
+    return false;   // (the caller falls through to the any-width kernel)
   // rows per wave (ASRX_TUNE_LN_RW = 1, 2 or 4; default 2: 9.4 -> 8.6 us at 15936 x 512)
   const int rw = (g_tune_ln_rw == 1 || g_tune_ln_rw == 4) ? g_tune_ln_rw : 2;
   const unsigned blocks = (unsigned)((rows + 4 * rw - 1) / (4 * rw));
@@ -374,6 +384,9 @@ bool ln_bwd_launch(int x_dtype, const void* x, int dy_dtype, const void* dy, con
                    const float* rstd, const float* dres, float* dx_out, void* dx_drop, int drop_dtype, float p,
                    uint64_t seed, float* part, int nblocks, int64_t rows, int d, hipStream_t st) {
   if (d != CH * NJ * 64) return false;
+  if (!ln_aligned<CH>(x, x_dtype) || !ln_aligned<CH>(dy, dy_dtype) || !ln_aligned<CH>(dres, ASRX_F32) ||
+      !ln_aligned<CH>(dx_out, ASRX_F32) || !ln_aligned<CH>(dx_drop, drop_dtype))
+    return false;   // (the caller falls through to the any-width kernel)
   const uint32_t thr = drop_threshold(p);
   const float sc = (p > 0.f && p < 1.f) ? 1.f / (1.f - p) : 1.f;
   hipLaunchKernelGGL((ln_bwd_kernel<CH, NJ>), dim3(nblocks), dim3(256), 0, st, x_dtype, x, dy_dtype, dy, gamma, mean,
@@ -495,7 +508,8 @@ extern "C" int asrx_layernorm_fwd(int32_t x_dtype, const void* x, int32_t y_dtyp
   if (rows == 0) return ASRX_OK;
   hipStream_t st = (hipStream_t)stream;
   const int pf = ln_pf();
-  if (d == 512 && x_dtype == ASRX_F32 && y_dtype == ASRX_BF16 && pf > 0 && ((uintptr_t)x | (uintptr_t)y) % 16 == 0) {
+  if (d == 512 && x_dtype == ASRX_F32 && y_dtype == ASRX_BF16 && pf > 0 &&
+      ((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) % 16 == 0) {
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 256 * ln_bpc()));
 #define ASRX_LNF(PF) hipLaunchKernelGGL((ln_fwd512_kernel<PF>), dim3(blocks), dim3(256), 0, st, (const float*)x, \
                                         (bf16_t*)y, gamma, beta, mean, rstd, rows, eps)
@@ -532,7 +546,8 @@ extern "C" int asrx_layernorm_bwd(int32_t x_dtype, const void* x, int32_t dy_dty
   const int pf = ln_pf();
   if (d == 512 && x_dtype == ASRX_F32 && (dy_dtype == ASRX_BF16 || dy_dtype == ASRX_F32) && pf > 0 &&
       (!dx_drop || drop_dtype == ASRX_BF16) &&
-      ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx_out | (uintptr_t)dres | (uintptr_t)dx_drop) % 16 == 0) {
+      ((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx_out | (uintptr_t)dres | (uintptr_t)dx_drop |
+       (uintptr_t)gamma) % 16 == 0) {
     const uint32_t thr = drop_threshold(dropout_p);
     const float sc = (dropout_p > 0.f && dropout_p < 1.f) ? 1.f / (1.f - dropout_p) : 1.f;
 #define ASRX_LNB(PF, DYF) hipLaunchKernelGGL((ln_bwd512_kernel<PF, DYF>), dim3(nblocks), dim3(64 * LNB_W), 0, st, \

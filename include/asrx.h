@@ -254,6 +254,8 @@ int asrx_softmax_bwd(int32_t dtype, const void* p, const void* dpd, void* ds, in
  * bwd: dx = rstd*(g - mean(g) - xhat*mean(g*xhat)), g = dy*gamma;  dx_out = dx + dres (dres nullable)
  *      if dx_drop != NULL also dx_drop = (drop_dtype)(dx_out * keep/(1-p))  (upstream sublayer's dropout bwd)
  *      per-block partial dgamma/dbeta go to part[nblocks][2][d]; finish with asrx_reduce_rows.
+ * Any d <= 2048 and any element-aligned pointers: the vector kernels (16-B fp32 / 8-B bf16 accesses) serve the
+ * calls whose tensor pointers are aligned to their access width, every other call takes the any-width kernels.
  * ------------------------------------------------------------------------------------------------- */
 int asrx_layernorm_fwd(int32_t x_dtype, const void* x, int32_t y_dtype, void* y, const float* gamma,
                        const float* beta, float* mean, float* rstd, int64_t rows, int32_t d, float eps,

@@ -1015,3 +1015,457 @@ def test_zero_spans_and_step_tokens():
     assert torch.equal(dec_in.view(B, L1 - 1), inp[:, :-1])
     assert torch.equal(tgt, text[:, 1:].reshape(-1))
     assert torch.equal(valid, (mask[:, :-1] >= 1).to(torch.uint8))
+
+
+# ------------------------------------------------------------------------------------------------
+# Dispatch edges of norm.hip (LayerNorm) against fp64 torch.  Tolerances are test_layernorm's: 1e-5 for fp32
+# results, 1e-2 for bf16 results (fp32 torch itself stays below 2.3e-7 of fp64 at these widths).
+
+F32, B16 = torch.float32, torch.bfloat16
+NAN = float("nan")
+
+
+def _ln_tol(dt):
+    return 1e-5 if dt == F32 else 1e-2
+
+
+def _ln_inputs(rows, d, xdt=F32, dyt=F32):
+    g = torch.Generator().manual_seed(1000 * rows + d)
+    x = (torch.randn(rows, d, generator=g) * 2 + 0.5).to(xdt)
+    gam = 1 + 0.1 * torch.randn(d, generator=g)
+    bet = 0.1 * torch.randn(d, generator=g)
+    dy = torch.randn(rows, d, generator=g).to(dyt)
+    dres = torch.randn(rows, d, generator=g)
+    return x, gam, bet, dy, dres
+
+
+def _ln_ref(x, gam, bet, dy):
+    """fp64 layer_norm of the (already rounded) inputs: y, mean, rstd, dx, dgamma, dbeta."""
+    xr, gr, br = (t.double().requires_grad_(True) for t in (x, gam, bet))
+    yr = torch.nn.functional.layer_norm(xr, (x.shape[1],), gr, br, 1e-5)
+    yr.backward(dy.double())
+    xd = x.double()
+    mean = xd.mean(1)
+    rstd = (xd.var(1, unbiased=False) + 1e-5).rsqrt()
+    return yr.detach(), mean, rstd, xr.grad, gr.grad, br.grad
+
+
+def _ln_check_stats(xd, mean, rstd, ref):
+    # (a row mean can lie near 0, where a relative error means nothing: its rounding error scales with the summed
+    #  elements, so it is measured against the largest |x|)
+    assert float((mean.cpu().double() - ref[1]).abs().max()) < 1e-5 * float(xd.float().abs().max())
+    assert relerr(rstd.cpu(), ref[2]) < 1e-5
+
+
+def _ln_check_fwd(xd, gd, bd, ydt, ref):
+    y = torch.full(xd.shape, NAN, device=dev, dtype=ydt)   # (NaN: an element the kernel skips fails the bound)
+    mean, rstd = K().layernorm_fwd(xd, gd, bd, y)
+    assert relerr(y.float().cpu(), ref[0]) < _ln_tol(ydt)
+    _ln_check_stats(xd, mean, rstd, ref)
+    return mean, rstd
+
+
+LN_ANY_WIDTHS = [8, 12, 65, 80, 1000]      # no CH x NJ x 64 instantiation: ln_fwd_any_kernel / ln_bwd_any_kernel
+LN_TEMPLATE_WIDTHS = [768, 1024, 2048]     # ln_fwd_kernel<4, 3 | 4 | 8>; ln_bwd_kernel<4, 3 | 4>, 2048: ln_bwd_any_kernel
+
+
+@pytest.mark.parametrize("rows", [1, 3, 37])
+@pytest.mark.parametrize("d", LN_ANY_WIDTHS + LN_TEMPLATE_WIDTHS)
+def test_layernorm_widths(d, rows):
+    """Forward and backward at the widths test_layernorm does not reach.  rows = 37: the backward's 3 blocks of 4
+    waves grid-stride over the rows; rows = 1: three of the block's waves hold only zero dgamma | dbeta partials;
+    d = 2048 backward: the any-width kernel with 8 * 2048 * 4 B = 64 KiB of dynamic LDS."""
+    x, gam, bet, dy, dres = _ln_inputs(rows, d)
+    ref = _ln_ref(x, gam, bet, dy)
+    xd, gd, bd = x.to(dev), gam.to(dev), bet.to(dev)
+    _ln_check_fwd(xd, gd, bd, B16, ref)
+    mean, rstd = _ln_check_fwd(xd, gd, bd, F32, ref)
+    dgb = torch.zeros(2 * d, device=dev)
+    drop = torch.full((rows, d), NAN, device=dev, dtype=B16)
+    dx = K().layernorm_bwd(xd, dy.to(dev), gd, mean, rstd, dgb, dres=dres.to(dev), dx_drop=drop)
+    want = ref[3] + dres.double()
+    assert relerr(dx.cpu(), want) < 1e-5
+    assert relerr(drop.float().cpu(), want) < 1e-2
+    assert relerr(dgb[:d].cpu(), ref[4]) < 1e-5
+    assert relerr(dgb[d:].cpu(), ref[5]) < 1e-5
+
+
+@pytest.mark.parametrize("rw", [1, 0, 4])
+@pytest.mark.parametrize("d", LN_TEMPLATE_WIDTHS)
+def test_layernorm_template_widths_rows_per_wave(d, rw, tuning):
+    """ln_fwd_kernel<4, NJ, RW> at NJ = 3, 4, 8 under every rows-per-wave variant (0 = the default 2); 37 rows leave
+    the last wave's row group ragged (row 36 alone) for RW = 2 and 4."""
+    tuning("ln_rw", rw)
+    x, gam, bet, dy, _ = _ln_inputs(37, d)
+    ref = _ln_ref(x, gam, bet, dy)
+    for ydt in (F32, B16):
+        _ln_check_fwd(x.to(dev), gam.to(dev), bet.to(dev), ydt, ref)
+
+
+@pytest.mark.parametrize("ydt", [B16, F32])
+@pytest.mark.parametrize("dyt", [B16, F32])
+@pytest.mark.parametrize("xdt", [B16, F32])
+@pytest.mark.parametrize("d", [80, 256, 512])
+def test_layernorm_operand_combinations(d, xdt, dyt, ydt):
+    """x / dy / y in bf16 and fp32, dres None or given, dx_drop None, bf16 or fp32 (p = 0: a copy of dx): at the
+    any-width kernels (80), the CH x NJ kernels (256; 512 unless the streaming kernels' operand types match) and
+    the d = 512 streaming kernels (x fp32, y bf16 forward; x fp32, dx_drop None or bf16 backward)."""
+    rows = 37
+    x, gam, bet, dy, dres = _ln_inputs(rows, d, xdt, dyt)
+    ref = _ln_ref(x, gam, bet, dy)
+    xd, gd, bd, dyd, dresd = (t.to(dev) for t in (x, gam, bet, dy, dres))
+    mean, rstd = _ln_check_fwd(xd, gd, bd, ydt, ref)
+    for with_dres in (False, True):
+        want = ref[3] + (dres.double() if with_dres else 0)
+        for ddt in (None, B16, F32):
+            dgb = torch.zeros(2 * d, device=dev)
+            drop = None if ddt is None else torch.full((rows, d), NAN, device=dev, dtype=ddt)
+            dx = K().layernorm_bwd(xd, dyd, gd, mean, rstd, dgb, dres=dresd if with_dres else None, dx_drop=drop)
+            assert relerr(dx.cpu(), want) < 1e-5, (with_dres, ddt)
+            if drop is not None:
+                assert relerr(drop.float().cpu(), want) < _ln_tol(ddt), (with_dres, ddt)
+            assert relerr(dgb[:d].cpu(), ref[4]) < 1e-5, (with_dres, ddt)
+            assert relerr(dgb[d:].cpu(), ref[5]) < 1e-5, (with_dres, ddt)
+
+
+@pytest.mark.parametrize("d,pf", [(512, 1), (512, 2), (512, 4), (512, 8), (256, 0), (80, 0)])
+def test_layernorm_dropout_copy(d, pf, tuning):
+    """dx_drop with p = 0.1: exactly 0 where the element stream's keep bit (rng_ref.elem_keep, element index
+    row * d + column) is 0, (dx + dres) / (1 - p) elsewhere; dx itself does not depend on p.  d = 512 under every
+    rows-in-flight variant of the streaming kernel (pf = 8: the CH x NJ kernel), 256 (CH x NJ), 80 (any width);
+    dy bf16 and fp32 (at d = 512 two instantiations), dx_drop bf16 and fp32 (fp32 leaves the streaming kernel)."""
+    from rng_ref import elem_keep
+    tuning("ln_pf", pf)
+    rows, p, seed = 37, 0.1, 20240611
+    keep = torch.from_numpy(elem_keep(seed, rows * d, p).reshape(rows, d))
+    assert 0 < int((~keep).sum()) < rows * d // 4
+    for dyt in (B16, F32):
+        x, gam, bet, dy, dres = _ln_inputs(rows, d, F32, dyt)
+        ref = _ln_ref(x, gam, bet, dy)
+        xd, gd, bd, dyd, dresd = (t.to(dev) for t in (x, gam, bet, dy, dres))
+        mean, rstd = _ln_check_fwd(xd, gd, bd, B16, ref)
+        want = ref[3] + dres.double()
+        for ddt in (B16, F32):
+            dgb = torch.zeros(2 * d, device=dev)
+            dx0 = K().layernorm_bwd(xd, dyd, gd, mean, rstd, dgb, dres=dresd,
+                                    dx_drop=torch.empty(rows, d, device=dev, dtype=ddt))
+            drop = torch.full((rows, d), NAN, device=dev, dtype=ddt)
+            dx = K().layernorm_bwd(xd, dyd, gd, mean, rstd, dgb, dres=dresd, dx_drop=drop, dropout_p=p, seed=seed)
+            assert torch.equal(dx, dx0)
+            assert relerr(dx.cpu(), want) < 1e-5
+            dc = drop.float().cpu()
+            assert bool((dc[~keep] == 0).all())
+            assert relerr(dc[keep], want[keep] / (1 - p)) < _ln_tol(ddt)
+
+
+def _offset_view(t, fill):
+    """A device copy of `t` that starts 2 elements (8 bytes of fp32, 4 of bf16) past a 16-B boundary, in the middle of
+    a buffer of `fill`."""
+    n = t.numel()
+    buf = torch.full((n + 16,), fill, device=dev, dtype=t.dtype)
+    v = buf[2:2 + n].view(t.shape)
+    v.copy_(t)
+    assert buf.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 2 * t.element_size()
+    return buf, v
+
+
+@pytest.mark.parametrize("which", ["all", "x", "dy", "dres", "y", "dx_drop"])
+@pytest.mark.parametrize("xdt,lowp", [(F32, B16), (F32, F32), (B16, B16)])
+@pytest.mark.parametrize("d", [256, 512])
+def test_layernorm_misaligned_views(d, xdt, lowp, which):
+    """Operands that are views starting off a 16-B boundary (all of them, or one at a time): asrx_layernorm_fwd / _bwd
+    route such calls to the any-width kernels' element accesses, whatever the d = 512 streaming kernels or the
+    CH x NJ kernels would have been chosen for the aligned call.  lowp: the dtype of dy, y and dx_drop."""
+    rows = 37
+    x, gam, bet, dy, dres = _ln_inputs(rows, d, xdt, lowp)
+    ref = _ln_ref(x, gam, bet, dy)
+
+    def place(name, t, fill=0.0):
+        return _offset_view(t, fill) if which in ("all", name) else (None, t.to(dev))
+
+    gd, bd = gam.to(dev), bet.to(dev)
+    _, xd = place("x", x)
+    _, dyd = place("dy", dy)
+    _, dresd = place("dres", dres)
+    ybuf, y = place("y", torch.full((rows, d), NAN, dtype=lowp), 512.0)
+    dbuf, drop = place("dx_drop", torch.full((rows, d), NAN, dtype=lowp), 512.0)
+    mean, rstd = K().layernorm_fwd(xd, gd, bd, y)
+    assert relerr(y.float().cpu(), ref[0]) < _ln_tol(lowp)
+    _ln_check_stats(xd, mean, rstd, ref)
+    dgb = torch.zeros(2 * d, device=dev)
+    dx = K().layernorm_bwd(xd, dyd, gd, mean, rstd, dgb, dres=dresd, dx_drop=drop)
+    want = ref[3] + dres.double()
+    assert relerr(dx.cpu(), want) < 1e-5
+    assert relerr(drop.float().cpu(), want) < _ln_tol(lowp)
+    assert relerr(dgb[:d].cpu(), ref[4]) < 1e-5
+    assert relerr(dgb[d:].cpu(), ref[5]) < 1e-5
+    for buf in (ybuf, dbuf):   # nothing written around the views
+        if buf is not None:
+            assert bool((buf[:2] == 512.0).all()) and bool((buf[2 + rows * d:] == 512.0).all())
+
+
+# ------------------------------------------------------------------------------------------------
+# Cross-entropy and greedy argmax (frontend.hip): every ce_rows_kernel<NJ>, ties, padding, ignored rows
+
+CE_SIZES = [(50, 50), (250, 256), (256, 256), (257, 320), (500, 512), (513, 576), (1000, 1024), (1024, 1024)]
+
+
+def _tied_logits(rows, V, ld):
+    """Logits on a grid of 0.5 (several rows hold their maximum more than once) and their padded copy [rows, ld]
+    whose columns [V, ld) are +inf: a kernel that reads a padding column fails loudly."""
+    g = torch.Generator().manual_seed(V)
+    x = (torch.randn(rows, V, generator=g) * 6).round() / 2
+    if rows < 37:   # (too few rows for a tie to be certain: one is planted)
+        x[0, V // 3] = x[0, V - 1] = x[0].max() + 0.5
+    ntied = int(((x == x.max(-1, keepdim=True).values).sum(-1) > 1).sum())
+    assert ntied >= 1, "the case no longer tests argmax ties"
+    full = torch.full((rows, ld), float("inf"))
+    full[:, :V] = x
+    return x, full
+
+
+def _ce_check(x, full, V, tgt, ignore_index, grad_scale, want_grad=True):
+    rows, ld = full.shape
+    loss, dl, am = K().cross_entropy(full.to(dev), V, tgt.to(dev), ignore_index=ignore_index, grad_scale=grad_scale,
+                                     want_grad=want_grad, want_argmax=True)
+    assert torch.equal(am.cpu(), x.argmax(-1))   # (torch.argmax: the first index of the maximum)
+    if want_grad:
+        assert dl.shape == (rows, ld) and dl.dtype == B16
+        assert bool((dl[:, V:] == 0).all())
+    else:
+        assert dl is None
+    if bool((tgt == ignore_index).all()):   # the library's documented value (torch gives NaN): loss 0, no gradient
+        assert float(loss) == 0.0
+        assert dl is None or bool((dl == 0).all())
+        return
+    lr = x.double().requires_grad_(True)
+    lref = torch.nn.functional.cross_entropy(lr, tgt, ignore_index=ignore_index)
+    lref.backward()
+    lref = lref.detach()
+    assert abs(float(loss) - float(lref)) < 1e-5 * abs(float(lref))
+    if want_grad:
+        assert relerr(dl[:, :V].float().cpu(), grad_scale * lr.grad) < 1e-2
+
+
+@pytest.mark.parametrize("rows", [1, 37, 130])
+@pytest.mark.parametrize("V,ld", CE_SIZES)
+def test_cross_entropy_sizes_ties_and_ignored_rows(V, ld, rows):
+    """ce_rows_kernel<4> (ld <= 256), <8> (ld <= 512) and <16> (ld <= 1024) with V at, below and just above the
+    64-column steps; rows = 37 and 130 leave the last block of 4 waves ragged.  Loss <= 1e-5 relative and dlogits
+    <= 1e-2 of grad_scale x the fp64 gradient, padding columns of dlogits 0, argmax torch's (first index)."""
+    x, full = _tied_logits(rows, V, ld)
+    g = torch.Generator().manual_seed(V + rows)
+    tgt = torch.randint(0, V, (rows,), generator=g)
+    some = tgt.clone()
+    some[5::7] = -100
+    _ce_check(x, full, V, some, -100, 1.0)
+    _ce_check(x, full, V, some, -100, 64.0)
+    _ce_check(x, full, V, some, -100, 64.0, want_grad=False)
+    zero = tgt.clone()           # ignore_index = 0: class 0 rows are the ignored ones
+    zero[0] = V - 1
+    zero[1::3] = 0
+    _ce_check(x, full, V, zero, 0, 0.125)
+    _ce_check(x, full, V, torch.full((rows,), -100), -100, 1.0)   # every row ignored
+    _ce_check(x, full, V, torch.zeros(rows, dtype=torch.int64), 0, 64.0)
+    _ce_check(x * 30, full * 30, V, some, -100, 1.0)              # sharp rows: most probabilities underflow
+
+
+def test_cross_entropy_refuses_row_strided_logits():
+    """The kernel writes dlogits with the logits' row stride: the wrapper, which allocates dlogits from the shape,
+    refuses a row-strided view instead of letting the kernel write past the buffer."""
+    rows, V = 8, 250
+    wide = torch.zeros(rows, 512, device=dev)
+    tgt = torch.zeros(rows, dtype=torch.int64, device=dev)
+    with pytest.raises(AssertionError):
+        K().cross_entropy(wide[:, :256], V, tgt)
+    loss, dl, _ = K().cross_entropy(wide[:, :256].contiguous(), V, tgt)
+    assert dl.shape == (rows, 256) and abs(float(loss) - math.log(V)) < 1e-5 * math.log(V)
+
+
+@pytest.mark.parametrize("rows", [1, 5, 130])
+@pytest.mark.parametrize("V,ld", [(50, 50), (50, 64), (250, 250), (250, 256), (1000, 1000), (1000, 1024)])
+def test_greedy_argmax(V, ld, rows):
+    """asrx_greedy_argmax: torch.argmax's first-index rule on tied rows, +inf padding columns ignored, a row of -inf
+    gives 0, the result lands in one column of the int64 token matrix (nothing else touched) and, if given, in cur."""
+    x, full = _tied_logits(rows, V, ld)
+    xi, fi = x.clone(), full.clone()
+    xi[rows // 2] = float("-inf")
+    fi[rows // 2, :V] = float("-inf")
+    L, t, mark = 7, 3, -7
+    for xv, fv in ((x, full), (xi, fi)):
+        want = xv.argmax(-1)
+        if xv is xi:
+            assert int(want[rows // 2]) == 0
+        for with_cur in (True, False):
+            tok = torch.full((rows, L), mark, dtype=torch.int64, device=dev)
+            cur = torch.full((rows,), mark, dtype=torch.int64, device=dev) if with_cur else None
+            K().greedy_argmax(fv.to(dev), V, tok[:, t], cur)
+            assert torch.equal(tok[:, t].cpu(), want)
+            if with_cur:
+                assert torch.equal(cur.cpu(), want)
+            tok[:, t] = mark
+            assert bool((tok == mark).all())
+
+
+# ------------------------------------------------------------------------------------------------
+# Elementwise kernels: asrx_cast, the grid-stride loops' second trip, asrx_rowwise, asrx_transpose_last2
+
+EW_BIG = (1 << 21) + 5   # the elementwise launches cap at 8192 blocks of 256: 5 threads take a second trip
+
+F32_EDGE_BITS = [
+    0x3F818000, 0x3F808000, 0xBF808000, 0xBF818000,   # exactly halfway, bf16 lsb odd / even (ties to even)
+    0x3F808001, 0x3F807FFF, 0x3F818001, 0x3F817FFF,   # just above / below halfway
+    0x00000000, 0x80000000, 0x7F800000, 0xFF800000,   # +-0, +-inf
+    0x00000001, 0x807FFFFF, 0x00008000, 0x00018000, 0x00400000,   # fp32 denormals (two of them halfway)
+    0x7F7FFFFF, 0xFF7FFFFF, 0x7F7F7FFF, 0x7F7F8000,   # the largest finite fp32 (rounds to inf) and its neighbours
+    0x7FC00000, 0x7F800001, 0xFFFFFFFF,               # NaN (one with only low mantissa bits set)
+]
+
+
+def _same_bits(got, want):
+    """bit-equal, NaN compared with isnan"""
+    got, want = got.cpu(), want.cpu()
+    assert got.dtype == want.dtype and got.shape == want.shape
+    nan = torch.isnan(want)
+    assert torch.equal(torch.isnan(got), nan)
+    it = torch.int32 if want.dtype == F32 else torch.int16
+    assert torch.equal(got.view(it)[~nan], want.view(it)[~nan])
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 100_003, EW_BIG])
+def test_cast(n):
+    """asrx_cast: fp32 -> bf16 bit-equal to torch's round-to-nearest-even conversion (halfway values of both
+    parities, signed zeros, infinities, denormals, the largest finite value; NaN stays NaN), bf16 -> fp32 and the
+    same-dtype copies exact."""
+    g = torch.Generator().manual_seed(n)
+    src = torch.randn(n, generator=g) * torch.exp(4 * torch.randn(n, generator=g))
+    edge = torch.from_numpy(np.array(F32_EDGE_BITS, dtype=np.uint32).view(np.float32).copy())
+    k = min(n, edge.numel())
+    src[:k] = edge[:k]
+    src[n - 1] = edge[0]   # (a tie that rounds up in the last element too: the second trip's at EW_BIG)
+    for s in (src, src.to(B16)):
+        for ddt in (B16, F32):
+            dst = torch.full((n,), NAN, device=dev, dtype=ddt)
+            K().cast(s.to(dev), dst)
+            _same_bits(dst, s.to(ddt))
+
+
+@pytest.mark.parametrize("dt", [F32, B16])
+def test_ewise_and_dropout_mask_second_grid_stride_trip(dt):
+    """test_ewise's checks at a size where the capped grids loop: every element, the last 5 included, against torch
+    and the numpy keep mask."""
+    from rng_ref import elem_keep
+    n = EW_BIG
+    g = torch.Generator(device=dev).manual_seed(5)
+    a = torch.randn(n, device=dev, generator=g).to(dt)
+    b = torch.randn(n, device=dev, generator=g).to(dt)
+    out = torch.full((n,), NAN, device=dev)
+    K().ewise(K().EW_RELU_GRAD, a, out, b=b)
+    assert torch.equal(out, torch.where(b > 0, a, torch.zeros((), dtype=dt, device=dev)).float())
+    p, seed = 0.1, 777
+    keep = torch.from_numpy(elem_keep(seed, n, p)).to(dev)
+    assert torch.equal(K().dropout_mask(n, p, seed, dev), keep.to(torch.uint8))
+    out.fill_(NAN)
+    K().ewise(K().EW_DROPOUT, a, out, p=p, seed=seed)
+    assert bool((out[~keep] == 0).all())
+    assert torch.allclose(out[keep], a.float()[keep] / (1 - p), rtol=1e-6, atol=0)
+    c = a.clone()
+    K().ewise(K().EW_ADD, c, c, b=b)
+    assert torch.equal(c, (a.float() + b.float()).to(dt))
+
+
+@pytest.mark.parametrize("rows,d,period", [(23, 1, 7), (23, 8, 23), (64, 80, 16), (37, 513, 5)])
+def test_rowwise(rows, d, period):
+    """asrx_rowwise: ROW_SCALE a * b[row], ROW_ADD a + b[row % period]; out of place and in place, exact in fp32."""
+    g = torch.Generator(device=dev).manual_seed(rows * d)
+    a = torch.randn(rows, d, device=dev, generator=g)
+    scale = torch.randn(rows, device=dev, generator=g)
+    add = torch.randn(period, d, device=dev, generator=g)
+    want_scale = a * scale[:, None]
+    want_add = a + add[torch.arange(rows, device=dev) % period]
+    for op, b, want in ((K().ROW_SCALE, scale, want_scale), (K().ROW_ADD, add, want_add)):
+        out = torch.full((rows, d), NAN, device=dev)
+        K().rowwise(op, a, b, out, period=period)
+        assert torch.equal(out, want)
+        inplace = a.clone()
+        K().rowwise(op, inplace, b, inplace, period=period)
+        assert torch.equal(inplace, want)
+
+
+@pytest.mark.parametrize("B,R,C", [(1, 1, 1), (3, 31, 33), (2, 80, 2), (5, 64, 97), (2, 200, 3)])
+def test_transpose_last2(B, R, C):
+    """asrx_transpose_last2 through its 32 x 33 LDS tile: partial tiles in both directions, exact."""
+    g = torch.Generator(device=dev).manual_seed(R * C)
+    x = torch.randn(B, R, C, device=dev, generator=g)
+    out = torch.full((B, C, R), NAN, device=dev)
+    K().transpose_last2(x, out)
+    assert torch.equal(out, x.transpose(1, 2).contiguous())
+
+
+# ------------------------------------------------------------------------------------------------
+# AdamW: the streaming kernel's two-vector main loop and the span kernel's unaligned bounds
+
+def test_adam_two_vector_main_loop():
+    """asrx_adam at n = 4 * (16384 * 256 + 1000) + 3: the grid is capped at 16384 blocks of 256 threads, so the
+    first 1000 threads take one trip of the two-vector main loop (i + stride < n / 4), every other thread the
+    single-vector step after it, and the last 3 elements the scalar tail.  Two steps with the bf16 shadow against
+    fp64 torch.optim.AdamW (test_embedding_and_ce_and_adam's bounds); the device-resident hyper-parameters (hyp)
+    give the scalar-argument call's bits."""
+    n = 4 * (16384 * 256 + 1000) + 3
+    lr, b1, b2, eps, wd = 1e-3, 0.9, 0.98, 1e-9, 0.01
+    g = torch.Generator(device=dev).manual_seed(11)
+    p0 = torch.randn(n, device=dev, generator=g)
+    gr = torch.randn(n, device=dev, generator=g)
+
+    def run(with_hyp):
+        p, m, v = p0.clone(), torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+        pb = torch.full((n,), NAN, device=dev, dtype=B16)
+        hyp = torch.empty(3, device=dev) if with_hyp else None
+        for step in (1, 2):
+            if with_hyp:   # (the scalar lr / step are then ignored: wrong on purpose)
+                K().adam_hyper(hyp, lr, b1, b2, step)
+                K().adam(p, gr * step, m, v, pb, 0.5, b1, b2, eps, wd, 9, decoupled=True, hyp=hyp)
+            else:
+                K().adam(p, gr * step, m, v, pb, lr, b1, b2, eps, wd, step, decoupled=True)
+        return p, m, v, pb
+
+    p, m, v, pb = run(False)
+    for a, b in zip((p, m, v, pb), run(True)):
+        assert torch.equal(a, b)
+    assert torch.equal(pb, p.to(B16))
+    pt = p0.cpu().double().requires_grad_(True)
+    opt = torch.optim.AdamW([pt], lr=lr, betas=(b1, b2), eps=eps, weight_decay=wd)
+    gc = gr.cpu().double()
+    for step in (1, 2):
+        pt.grad = gc * step
+        opt.step()
+    assert relerr(p.cpu(), pt.detach()) < 1e-6
+    assert relerr(pb.float().cpu(), pt.detach()) < 1e-2
+
+
+@pytest.mark.parametrize("decoupled", [True, False])
+def test_adam_spans_unaligned_bounds(decoupled):
+    """asrx_adam_spans over bounds that are not multiples of 4 (heads, tails, spans inside one 4-group, an empty
+    span): inside the spans p, m, v and the bf16 shadow carry the bits of asrx_adam over the whole buffer (adam_elem
+    pins one rounding sequence), outside them nothing is touched."""
+    n = 100_003
+    spans = [(0, 5), (5, 7), (7, 8), (9, 4099), (4100, 4104), (5001, 5003), (6000, 6000), (70001, 100003)]
+    g = torch.Generator(device=dev).manual_seed(13)
+    p0 = torch.randn(n, device=dev, generator=g)
+    gr = torch.randn(n, device=dev, generator=g)
+    m0 = 0.1 * torch.randn(n, device=dev, generator=g)
+    v0 = 0.01 * torch.rand(n, device=dev, generator=g)
+    s0 = torch.full((n,), 3.0, device=dev, dtype=B16)
+    hyper = (1e-3, 0.9, 0.98, 1e-9, 0.01, 3)
+    full = [p0.clone(), m0.clone(), v0.clone(), s0.clone()]
+    K().adam(full[0], gr, full[1], full[2], full[3], *hyper, grad_scale=0.5, decoupled=decoupled)
+    got = [p0.clone(), m0.clone(), v0.clone(), s0.clone()]
+    K().adam_spans(got[0], gr, got[1], got[2], got[3], torch.tensor(spans, dtype=torch.int64, device=dev), *hyper,
+                   grad_scale=0.5, decoupled=decoupled)
+    inside = torch.zeros(n, dtype=torch.bool, device=dev)
+    for a, e in spans:
+        inside[a:e] = True
+    for name, x, f, orig in zip("pmvs", got, full, (p0, m0, v0, s0)):
+        assert torch.equal(x[inside], f[inside]), name
+        assert torch.equal(x[~inside], orig[~inside]), name
+        assert not torch.equal(f[inside], orig[inside]), name

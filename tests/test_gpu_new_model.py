@@ -116,7 +116,9 @@ def test_new_evaluate_fp32_golden(golden_dir, name):
 def test_new_evaluate_kv_cache_equals_full_prefix_recompute(precision):
     """The KV-cached greedy decode (Decoder._evaluate_cached, the default) against the reference's full-prefix
     recompute of every step (evaluate(..., cache=False), new/model.py:125-142) on the same weights: token rows and
-    EOS steps exact, the final step's logits (every position) within fp32 / bf16 rounding."""
+    EOS steps exact, the final step's logits (every position) within fp32 rounding; bf16: the logits of every
+    position whose inputs are identical in both paths within 2e-2, more than one position per row on average
+    (synthetic_batch seed 11)."""
     m, c = build("new_small", precision)
     m.eval()
     s, lens, text = N.synthetic_batch(c, 5, seed=11)
@@ -127,10 +129,18 @@ def test_new_evaluate_kv_cache_equals_full_prefix_recompute(precision):
     assert l0.shape == l1.shape and t0.shape == t1.shape and t1.dtype == torch.int32
     if precision == "bf16":
         # (bf16: the two paths run GEMMs of different row counts, whose fp32 sums may round an activation
-        #  differently; a near-tie can then flip a token and every later position with it — the first position,
-        #  computed from identical inputs, is compared)
-        assert relerr(l1[:, 0], l0[:, 0].cpu()) < 2e-2
+        #  differently; a near-tie can then flip a token and every later position with it — per row, the positions
+        #  up to and including the first step whose tokens differ are computed from identical inputs and compared)
+        s0, s1 = t0[:, 1:].cpu(), t1[:, 1:].cpu()
+        rows, steps = s0.shape
+        same_inputs = torch.zeros(rows, steps, dtype=torch.bool)
+        for r in range(rows):
+            flips = (s0[r] != s1[r]).nonzero()
+            same_inputs[r, :int(flips[0]) + 1 if flips.numel() else steps] = True
+        assert relerr(l1.cpu()[same_inputs], l0.cpu()[same_inputs]) < 2e-2
         assert int(t1.min()) >= 0 and int(t1.max()) < c.vocab_size
+        compared = int(same_inputs.sum())
+        assert compared > rows, f"{compared} positions compared over {rows} rows: none past position 0"
         return
     assert torch.equal(t0.cpu(), t1.cpu())
     assert torch.equal(e0, e1)
