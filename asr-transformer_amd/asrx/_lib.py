@@ -134,6 +134,9 @@ SIGNATURES = {
     "asrx_ewise": [c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i64, c_f32, c_u64, c_vp],
     "asrx_sum_chunks_bf16": [c_vp, c_i32, c_i64, c_vp, c_vp],
     "asrx_greedy_argmax": [c_vp, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp],
+    "asrx_beam_step": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                       c_vp, c_vp, c_vp],
+    "asrx_gather_rows": [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp],
     "asrx_spectrogram": [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_vp, c_i64,
                          c_vp, c_vp],
     "asrx_adam": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_i32,

@@ -5,6 +5,7 @@ flat gradient buffer that `p.grad` views (asrx.params); the Functions return Non
 `model_forward` / `model_backward` are also used directly (no autograd) by the fused trainer (asrx.train).
 """
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -509,6 +510,47 @@ def _decoder_evaluate_recompute(dec, x, enc_x):
     return decoder_input, probs
 
 
+def _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te):
+    """One decoder position for B samples x W hypotheses (rows b*W + w): the embedding of `cur` at position t through
+    every layer (pe = the positional table), returning the fp32 stream [B*W, d].  kvs [n][B*W][P][2d] are the
+    self-attention K/V caches, which gain position t; kvx [B*Te][n*2d] holds every layer's cross-attention K/V per
+    SAMPLE: the W hypotheses of a sample share it, so cross-attention runs as batch = B with W queries each (W = 1:
+    greedy decoding)."""
+    dev = cur.device
+    d, H, n = dec.emb_dim, dec.num_heads, len(dec._layers)
+    dh = d // H
+    R, P = B * W, kvs.shape[2]
+    scale = d ** -0.5
+    xs = torch.empty(R, d, dtype=torch.float32, device=dev)
+    K.embed_fwd(cur, dec._embedding.weight.data, pe[t:t + 1], xs, 1)
+    for l, layer in enumerate(dec._layers):
+        mha, cr = layer._mask_attention, layer._cross_attention
+        # masked self-attention: the new position's K/V join the cache, its query attends to positions 0..t
+        h, _, _ = Bk.ln_fwd(C, xs, layer._norm1)
+        q = torch.empty(R, d, dtype=C.cd, device=dev)
+        wqkv, bqkv = C.W(mha.wqkv), mha.bqkv.data
+        K.linear(h, wqkv[:d], q, bias=bqkv[:d])
+        cache = kvs[l]
+        K.gemm(h, wqkv[d:], cache[:, t], R, 2 * d, d, lda=d, ldb=d, ldc=P * 2 * d, bias=bqkv[d:])
+        o = torch.empty(R, d, dtype=C.cd, device=dev)
+        st = ((d, d), (2 * d, P * 2 * d), (2 * d, P * 2 * d), (d, d))
+        Bk.attn_fwd(C, q, cache, cache[:, :, d:], o, R, H, 1, t + 1, dh, st, scale, MaskSpec())
+        x1 = torch.empty(R, d, dtype=torch.float32, device=dev)
+        K.linear(o, C.W(mha._out_linear.weight), x1, bias=mha._out_linear.bias.data, resid=xs, ld_resid=d)
+        # cross-attention over the encoder output (no mask, model.py:71)
+        h2, _, _ = Bk.ln_fwd(C, x1, layer._norm2)
+        q2 = torch.empty(R, d, dtype=C.cd, device=dev)
+        K.linear(h2, C.W(cr.wq), q2, bias=cr.bq.data)
+        o2 = torch.empty(R, d, dtype=C.cd, device=dev)
+        kv_l = kvx[:, l * 2 * d:]
+        st2 = ((d, W * d), (n * 2 * d, Te * n * 2 * d), (n * 2 * d, Te * n * 2 * d), (d, W * d))
+        Bk.attn_fwd(C, q2, kv_l, kv_l[:, d:], o2, B, H, W, Te, dh, st2, scale, MaskSpec())
+        x2 = torch.empty(R, d, dtype=torch.float32, device=dev)
+        K.linear(o2, C.W(cr._out_linear.weight), x2, bias=cr._out_linear.bias.data, resid=x1, ld_resid=d)
+        xs, _ = Bk.ffn_fwd(C, x2, layer._norm3, layer._feedforward)
+    return xs
+
+
 def _decoder_evaluate_cached(dec, x, enc_x):
     C = make_ctx(dec, 0.0)
     C.train, C.p = False, 0.0
@@ -535,35 +577,8 @@ def _decoder_evaluate_cached(dec, x, enc_x):
     tokens = torch.empty(B, L0 + steps, dtype=torch.int64, device=dev)
     tokens[:, :L0] = x.to(device=dev, dtype=torch.int64)
     cur = tokens[:, 0].contiguous()
-    scale = d ** -0.5
     for t in range(P):
-        xs = torch.empty(B, d, dtype=torch.float32, device=dev)
-        K.embed_fwd(cur, dec._embedding.weight.data, pe[t:t + 1], xs, 1)
-        for l, layer in enumerate(dec._layers):
-            mha, cr = layer._mask_attention, layer._cross_attention
-            # masked self-attention: the new position's K/V join the cache, its query attends to positions 0..t
-            h, _, _ = Bk.ln_fwd(C, xs, layer._norm1)
-            q = torch.empty(B, d, dtype=C.cd, device=dev)
-            wqkv, bqkv = C.W(mha.wqkv), mha.bqkv.data
-            K.linear(h, wqkv[:d], q, bias=bqkv[:d])
-            cache = kvs[l]
-            K.gemm(h, wqkv[d:], cache[:, t], B, 2 * d, d, lda=d, ldb=d, ldc=P * 2 * d, bias=bqkv[d:])
-            o = torch.empty(B, d, dtype=C.cd, device=dev)
-            st = ((d, d), (2 * d, P * 2 * d), (2 * d, P * 2 * d), (d, d))
-            Bk.attn_fwd(C, q, cache, cache[:, :, d:], o, B, H, 1, t + 1, dh, st, scale, MaskSpec())
-            x1 = torch.empty(B, d, dtype=torch.float32, device=dev)
-            K.linear(o, C.W(mha._out_linear.weight), x1, bias=mha._out_linear.bias.data, resid=xs, ld_resid=d)
-            # cross-attention over the encoder output (no mask, model.py:71)
-            h2, _, _ = Bk.ln_fwd(C, x1, layer._norm2)
-            q2 = torch.empty(B, d, dtype=C.cd, device=dev)
-            K.linear(h2, C.W(cr.wq), q2, bias=cr.bq.data)
-            o2 = torch.empty(B, d, dtype=C.cd, device=dev)
-            kv_l = kvx[:, l * 2 * d:]
-            st2 = ((d, d), (n * 2 * d, Te * n * 2 * d), (n * 2 * d, Te * n * 2 * d), (d, d))
-            Bk.attn_fwd(C, q2, kv_l, kv_l[:, d:], o2, B, H, 1, Te, dh, st2, scale, MaskSpec())
-            x2 = torch.empty(B, d, dtype=torch.float32, device=dev)
-            K.linear(o2, C.W(cr._out_linear.weight), x2, bias=cr._out_linear.bias.data, resid=x1, ld_resid=d)
-            xs, _ = Bk.ffn_fwd(C, x2, layer._norm3, layer._feedforward)
+        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, 1, Te)
         hc = torch.empty(B, d, dtype=C.cd, device=dev)       # no final LayerNorm in evaluate (model.py:142)
         K.cast(xs, hc)
         lg = logits[:, t]
@@ -581,6 +596,142 @@ def _decoder_evaluate_cached(dec, x, enc_x):
             if int(tok[s, Li]) == eos or i == steps:
                 probs.append(logits[s:s + 1, :Li - 1, :V].squeeze())
     return tokens[B - 1:B].to(x.dtype), probs
+
+
+class BeamResult(NamedTuple):
+    """Decoder.beam_search / Transformer.beam_search: per sample the `nbest` best hypotheses, best first.
+    tokens (B, nbest, L0 + steps) int64: prompt, generated tokens, EOS after a hypothesis's end (steps = max_len
+    unless polling stopped the loop early); lengths (B, nbest) int64: generated tokens, the EOS included; scores
+    (B, nbest) fp32: summed log-probabilities (-inf: fewer than nbest hypotheses exist)."""
+    tokens: torch.Tensor
+    lengths: torch.Tensor
+    scores: torch.Tensor
+
+
+def beam_backtrack(parents, toks):
+    """Follow the parent links of a beam history back from the last step.  parents / toks: [steps][B][W] integer
+    arrays (the slot a step's hypothesis extends, the token it adds).  Returns [B][W][steps]: the token sequence of
+    every final slot."""
+    parents, toks = torch.as_tensor(parents), torch.as_tensor(toks)
+    steps, B, W = toks.shape
+    out = torch.empty(B, W, steps, dtype=torch.int64)
+    slot = torch.arange(W).expand(B, W)
+    for s in range(steps - 1, -1, -1):
+        out[:, :, s] = toks[s].gather(1, slot)
+        slot = parents[s].gather(1, slot).long()
+    return out
+
+
+def beam_rank(scores, lengths, length_penalty):
+    """Order of each sample's W hypotheses: descending score / len**length_penalty, ties by slot, dead (-inf or
+    NaN) hypotheses last.  scores fp32 [B][W], lengths [B][W]; returns int64 [B][W] slot numbers."""
+    key = scores.double()
+    if length_penalty != 0.0:
+        key = key / lengths.clamp(min=1).double() ** float(length_penalty)
+    key = torch.where(torch.isfinite(scores), key, torch.full_like(key, float("-inf")))
+    return torch.sort(key, dim=1, descending=True, stable=True).indices
+
+
+@torch.no_grad()
+def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8):
+    """Beam-search decoding on the KV-cached decoder (the reference has none: Decoder.evaluate, model.py:125-151, is
+    greedy).  x (B, L0 >= 1) is the prompt, prefilled with teacher forcing; `max_len` new tokens (default seq_len)
+    are then chosen with `beam` hypotheses per sample, each step keeping the `beam` best continuations by summed
+    log-probability (ties: lower parent slot, then lower token id); a hypothesis that emitted EOS is frozen.  The
+    hypotheses are finally ranked by score / len**length_penalty (len counts the generated tokens, EOS included).
+
+    final_norm=True (default) applies the decoder's last LayerNorm before the classifier, as Decoder.forward does
+    (model.py:122) and as models are therefore trained; final_norm=False reproduces the logits of `evaluate`, which
+    skips it (model.py:142).
+
+    Everything per step runs on the device (asrx_beam_step picks the slots, asrx_gather_rows reorders the K/V
+    caches into their second buffer); the host reads nothing until the end, except every `poll` steps (0 = never)
+    the count of live hypotheses, to stop once all have finished.  Eval only: dropout is off."""
+    C = make_ctx(dec, 0.0)
+    C.train, C.p = False, 0.0
+    dev = enc_x.device
+    B, Te, d = enc_x.shape
+    n = len(dec._layers)
+    W = int(beam)
+    steps = dec._seq_len if max_len is None else int(max_len)
+    nbest, poll = int(nbest), int(poll)
+    if not 1 <= W <= 16:
+        raise ValueError(f"beam must be in 1..16, got {beam}")
+    if not 1 <= nbest <= W:
+        raise ValueError(f"nbest must be in 1..beam, got {nbest}")
+    if x.dim() != 2 or x.shape[0] != B or x.shape[1] < 1:
+        raise ValueError(f"prompt must be (B, L0 >= 1) with B = {B}, got {tuple(x.shape)}")
+    if steps < 0 or poll < 0:
+        raise ValueError("max_len and poll must be >= 0")
+    cls = dec._classifier
+    V, Vp = cls.V, cls.Vp
+    eos = int(dec._eos_token_id)
+    L0 = x.shape[1]
+    P = L0 - 1 + steps
+    pe = dec._pe.pe[0]
+    if P > pe.shape[0]:
+        raise ValueError(f"decoder length {P} exceeds the PE table ({pe.shape[0]}) as in layers.py:73")
+    prompt = x.to(device="cpu", dtype=torch.int64)
+    if B == 0 or steps == 0:
+        return BeamResult(prompt[:, None, :].expand(B, nbest, L0).contiguous(),
+                          torch.zeros(B, nbest, dtype=torch.int64), torch.zeros(B, nbest, dtype=torch.float32))
+    R = B * W
+    enc_c = torch.empty(B * Te, d, dtype=C.cd, device=dev)
+    K.cast(enc_x.reshape(B * Te, d).contiguous(), enc_c)
+    Wkv, bkv, _, _ = _kv_block(C, dec)
+    kvx = torch.empty(B * Te, n * 2 * d, dtype=C.cd, device=dev)       # cross-attention K/V: per sample, not per beam
+    K.linear(enc_c, Wkv, kvx, bias=bkv)
+    kvs = torch.empty(n, R, P, 2 * d, dtype=C.cd, device=dev)           # self-attention K/V caches and, for W > 1,
+    kvs_alt = torch.empty_like(kvs) if W > 1 else None                  # the buffer each reorder gathers into
+    xr = prompt.to(dev).repeat_interleave(W, dim=0)                     # (R, L0): every beam starts on the prompt
+    score0 = torch.full((B, W), float("-inf"), dtype=torch.float32)
+    score0[:, 0] = 0.0                                                  # one live root: the others can only lose
+    state = (score0.reshape(R).to(dev), torch.zeros(R, dtype=torch.uint8, device=dev),
+             torch.zeros(R, dtype=torch.int32, device=dev))
+    other = tuple(torch.empty_like(a) for a in state)
+    tok_h = torch.empty(steps, R, dtype=torch.int64, device=dev)
+    par_h = torch.empty(steps, R, dtype=torch.int32, device=dev)
+    src_row = torch.empty(R, dtype=torch.int32, device=dev)
+    n_live = torch.zeros(steps, dtype=torch.int32, device=dev)          # one zeroed word per step
+    cur = xr[:, 0].contiguous()
+    done = steps
+    for t in range(P):
+        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te)
+        s = t - (L0 - 1)
+        if s < 0:
+            cur = xr[:, t + 1].contiguous()
+            continue
+        if final_norm:
+            hc, _, _ = Bk.ln_fwd(C, xs, dec._norm_layer)
+        else:
+            hc = torch.empty(R, d, dtype=C.cd, device=dev)
+            K.cast(xs, hc)
+        lg = torch.empty(R, Vp, dtype=torch.float32, device=dev)
+        K.gemm(hc, C.W(cls.weight), lg, R, Vp, d, lda=d, ldb=d, ldc=Vp)
+        K.beam_step(lg, V, B, W, eos, state, other, tok_h[s], par_h[s], src_row, cur=cur, n_live=n_live[s:s + 1])
+        state, other = other, state
+        if poll and (s + 1) % poll == 0 and s + 1 < steps and int(n_live[s]) == 0:
+            done = s + 1
+            break
+        if W > 1 and s + 1 < steps:      # (one beam: the parent is always slot 0, the cache stays in place)
+            K.gather_rows(kvs, kvs_alt, src_row, n, R, (t + 1) * 2 * d, P * 2 * d, R * P * 2 * d)
+            kvs, kvs_alt = kvs_alt, kvs
+    score, _, length = (a.cpu().view(B, W) for a in state)
+    seqs = beam_backtrack(par_h[:done].cpu().view(done, B, W), tok_h[:done].cpu().view(done, B, W))
+    order = beam_rank(score, length, length_penalty)[:, :nbest]
+    best = seqs.gather(1, order[:, :, None].expand(-1, -1, done))
+    tokens = torch.cat([prompt[:, None, :].expand(B, nbest, L0), best], dim=2)
+    return BeamResult(tokens, length.long().gather(1, order), score.gather(1, order))
+
+
+def transformer_beam_search(model, spectrum, text=None, **kw):
+    """Transformer.beam_search: front end and encoder as in `evaluate` (model.py:201-206), then
+    decoder_beam_search.  text=None starts every sample on a BOS column (id 1)."""
+    with torch.no_grad():
+        enc = model.encoder(model.input_layer(spectrum))
+    if text is None:
+        text = torch.ones(spectrum.shape[0], 1, dtype=torch.int64)
+    return decoder_beam_search(model.decoder, text, enc, **kw)
 
 
 @torch.no_grad()

@@ -725,6 +725,35 @@ def greedy_argmax(logits, V, tok_col, cur=None):
          tok_col.stride(0), _p(cur), stream())
 
 
+def beam_step(logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur=None, n_live=None):
+    """One beam-selection step (asrx_beam_step): logits fp32 [B*W, ld]; state_* = (score fp32, fin uint8, len int32),
+    each [B*W], two distinct sets; tok int64 / parent int32 / src_row int32 [B*W] take the chosen slots, cur (int64
+    [B*W], optional) the next step's tokens; n_live (int32 [1], optional, zero on entry) gains the count of
+    unfinished slots."""
+    (si, fi, li), (so, fo, lo) = state_in, state_out
+    _cuda(logits, si, fi, li, so, fo, lo, tok, parent, src_row, cur, n_live)
+    R = B * W
+    assert logits.dtype == torch.float32 and logits.shape[0] == R and logits.stride(1) == 1
+    for a, dt in ((si, torch.float32), (so, torch.float32), (fi, torch.uint8), (fo, torch.uint8), (li, torch.int32),
+                  (lo, torch.int32), (tok, torch.int64), (parent, torch.int32), (src_row, torch.int32),
+                  (cur, torch.int64)):
+        assert a is None or (a.dtype == dt and a.numel() == R and a.is_contiguous())
+    assert n_live is None or (n_live.dtype == torch.int32 and n_live.numel() == 1)
+    call("asrx_beam_step", logits.data_ptr(), B, W, V, logits.stride(0), si.data_ptr(), fi.data_ptr(), li.data_ptr(),
+         int(eos), so.data_ptr(), tok.data_ptr(), _p(cur), parent.data_ptr(), src_row.data_ptr(), fo.data_ptr(),
+         lo.data_ptr(), _p(n_live), stream())
+
+
+def gather_rows(src, dst, index, outer, rows, count, row_stride, outer_stride):
+    """dst[o][r][:count] = src[o][index[r]][:count] (asrx_gather_rows) over two buffers of one layout (bf16 or
+    fp32, strides in elements); index int32 [rows] holds row numbers in [0, rows)."""
+    _cuda(src, dst, index)
+    assert src.dtype == dst.dtype and src.element_size() in (2, 4)
+    assert index.dtype == torch.int32 and index.numel() == rows and index.is_contiguous()
+    call("asrx_gather_rows", src.data_ptr(), dst.data_ptr(), index.data_ptr(), src.element_size(), outer, rows,
+         count, row_stride, outer_stride, stream())
+
+
 def sum_chunks_bf16(recv, world, chunk, out):
     """out[i] = bf16(sum_w recv[w * chunk + i]) with an fp32 sum (bf16-wire gradient exchange, asrx.dist)."""
     _cuda(recv, out)

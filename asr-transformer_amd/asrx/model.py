@@ -197,6 +197,11 @@ class Decoder(nn.Module):
         from .functions import decoder_evaluate
         return decoder_evaluate(self, x, enc_x)
 
+    def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8):
+        """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult."""
+        from .functions import decoder_beam_search
+        return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll)
+
 
 class Transformer(nn.Module):
     """model.py:154-206.  forward(spectrum (B,1,F,T), text (B,L) int, mask (B,L)) -> logits (B,L,V)."""
@@ -226,3 +231,8 @@ class Transformer(nn.Module):
     def evaluate(self, spectrum, text):
         from .functions import transformer_evaluate
         return transformer_evaluate(self, spectrum, text)
+
+    def beam_search(self, spectrum, text=None, **kw):
+        """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1)."""
+        from .functions import transformer_beam_search
+        return transformer_beam_search(self, spectrum, text, **kw)

@@ -32,7 +32,8 @@ extern "C" {
 #define ASRX_BITS 2   /* gate operand only: 1 bit per element, uint32 words (ld in words; see mask_out) */
 
 /* Library version / build identification (3: dq_acc holds one slab per key block, asrx_attn_dq_acc_elems;
- * asrx_adam_spans takes bounds that are not multiples of 4). */
+ * asrx_adam_spans takes bounds that are not multiples of 4.  4: asrx_beam_step and asrx_gather_rows, the device half
+ * of beam-search decoding). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -373,6 +374,34 @@ int asrx_spectrogram(const float* audio, int64_t batch, int64_t samples, int64_t
  * if cur != NULL, at cur[r] (the next step's embedding input). */
 int asrx_greedy_argmax(const float* logits, int64_t rows, int32_t V, int64_t ld, int64_t* tok, int64_t tok_stride,
                        int64_t* cur, void* stream);
+
+/* One beam-search decode step for B samples x W beams (Decoder.beam_search; the reference decodes greedily only,
+ * model.py:125-151): the per-sample top-W over the W x V continuation scores, one launch, no host round trip.
+ *   logits    fp32, B*W rows (sample b, beam w at row b*W + w), row stride ld >= V; only columns [0, V) are read
+ *   score_in  fp32 [B*W] running log-probabilities, fin_in uint8 [B*W] finished flags, len_in int32 [B*W] lengths
+ * Candidates of sample b: a live beam w offers every v < V at score_in[w] + logits[w][v] - logsumexp(logits[w][:V])
+ * (max-subtracted, fp32); a finished beam offers exactly (w, eos) at score_in[w].  A NaN score reads as -inf.  The W
+ * best by descending score, ties by ascending flat index w*V + v (the first-index rule of asrx_greedy_argmax, which
+ * W = 1 reduces to), go to slots b*W + j, j = 0 the best; -inf candidates are legal and rank last in index order.
+ * Per slot: score_out, tok_out (int64; also cur[slot] if cur != NULL, the next step's embedding input), parent_out
+ * (int32 in [0, W)), src_row_out = b*W + parent (the asrx_gather_rows index), fin_out = fin_in[parent] | (tok ==
+ * eos), len_out = len_in[parent] + (fin_in[parent] ? 0 : 1).  n_live (optional, device int32): the number of
+ * unfinished slots over the whole batch is ADDED to it (integer atomics, deterministic), so it must hold 0 before
+ * the call.  Outputs must not alias inputs (the caller ping-pongs two state sets).
+ * 1 <= W <= 16, 0 <= eos < V, any ld; V above 2^20 returns ASRX_ERR_UNSUPPORTED.  One workgroup per sample; the
+ * candidates are held in LDS while W*V <= 16128, else formed again from the logits in every round. */
+int asrx_beam_step(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, const float* score_in,
+                   const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out, int64_t* tok_out,
+                   int64_t* cur, int32_t* parent_out, int32_t* src_row_out, uint8_t* fin_out, int32_t* len_out,
+                   int32_t* n_live, void* stream);
+/* Row gather, the beam reorder of the K/V caches: dst[o][r][0:count) = src[o][index[r]][0:count) for o < outer,
+ * r < rows; both buffers share one layout (row_stride >= count and outer_stride in elements of esize = 2 or 4
+ * bytes), index = device int32 row numbers in [0, rows) (a row with any other index is left untouched).  Elements
+ * of dst beyond count in a row are not written.  16-byte accesses when both bases, the strides and count allow it,
+ * element accesses otherwise.  src and dst must not overlap (ASRX_ERR_ARG): the caller double-buffers.  One launch
+ * covers every decoder layer: outer = layers, rows = B*W, count = the filled prefix of a cache row. */
+int asrx_gather_rows(const void* src, void* dst, const int32_t* index, int32_t esize, int32_t outer, int32_t rows,
+                     int64_t count, int64_t row_stride, int64_t outer_stride, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
