@@ -96,7 +96,9 @@ ASRX_DEV float fmx(float a, float b) { return __builtin_elementwise_maximum(a, b
 constexpr float kLazy = 8.f;
 
 ASRX_DEV bool masked(const AttnArgs& a, int b, int q, int key) {
-  if (key >= a.Lk) return true;
+  // (q >= Lq: the resident kernels' last query chunk asks for rows that belong to no query; a dense mask has no
+  //  bytes for them — for the last batch they lie past the end of the mask's allocation)
+  if (key >= a.Lk || q >= a.Lq) return true;
   if (a.mode == 1) {
     if (a.causal && key > q) return true;
     if (a.kvalid && !a.kvalid[b * a.validb + key]) return true;
