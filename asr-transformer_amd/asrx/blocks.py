@@ -174,19 +174,36 @@ class Seeds:
         return x ^ (x >> 31)
 
 
-# Fixed choices whose A/B switches were removed in round 5 (measurements in DESIGN §4):
+# Fixed choices of the training path (their A/B runs ended in round 5; measurements in DESIGN §4):
 # * the FFN hidden layer's ReLU/dropout mask is kept as bits for the data gradient (not re-read from the bf16 f);
 # * the attention keep bits are generated inside the preceding LayerNorm's launch, for the decoder's
 #   cross-attention too (round 4);
 # * weight gradients are not issued per layer on a side stream (no gain: they compete with the backward chain
 #   for the same CUs), nor the keep bits (18.2 vs 17.75 ms/step: the VALU-heavy generator stole the GEMM's CUs).
-GATE_BITS = True
-LN_DROPGEN = True
-LN_DROPGEN_CROSS = True
 
 
 def _empty(shape, dtype, like):
     return torch.empty(shape, dtype=dtype, device=like.device)
+
+
+def as_dtype(t, dtype):
+    """t (contiguous) in `dtype` — the native cast kernel when it differs."""
+    if t.dtype == dtype:
+        return t.contiguous()
+    out = _empty(t.shape, dtype, t)
+    K.cast(t.contiguous(), out)
+    return out
+
+
+def drop_bwd_c(C, g, seed):
+    """dropout_bwd of an output gradient, in the compute dtype: the forward epilogue's element mask (same seed and
+    element index) and scale, or a plain cast without dropout."""
+    dy_c = _empty(g.shape, C.cd, g)
+    if C.p > 0:
+        K.ewise(K.EW_DROPOUT, g, dy_c, p=C.p, seed=seed)
+    else:
+        K.cast(g, dy_c)
+    return dy_c
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
@@ -219,23 +236,21 @@ def ln_bwd(C, x, dy, ln, mean, rstd, dres=None, drop_out=None, drop_seed=0, drop
 
 # ------------------------------------------------------------------------------------------------ attention
 
-def attn_prepare(C, B, H, Lq, Lk, dh, device):
+def attn_prepare(C):
     """Draw the attention-dropout seed (the keep bits themselves come from the preceding LayerNorm's launch where
     ln_fwd_attn applies, else from the attention forward's own launch)."""
-    return {"seed": C.seed(), "dropmask": None, "event": None}
+    return {"seed": C.seed(), "dropmask": None, "ready": False}
 
 
 def attn_fwd(C, q, k, v, o, B, H, Lq, Lk, dh, strides, scale, spec, prep=None):
     """Fused LDS-tiled kernel on the bf16 path; materialised scores + row softmax otherwise."""
     if prep is None:
-        prep = {"seed": C.seed(), "dropmask": None, "event": None}
+        prep = attn_prepare(C)
     seed = prep["seed"]
     S = {"seed": seed, "spec": spec, "dims": (B, H, Lq, Lk, dh), "strides": strides, "scale": scale}
     if C.cd == torch.bfloat16 and C.attn_impl == "fused" and dh in (32, 64):
-        dm, ready = prep["dropmask"], prep["event"] is not None or prep.get("ready", False)
-        if prep["event"] is not None:
-            torch.cuda.current_stream(q.device).wait_event(prep["event"])
-        elif not ready:
+        dm, ready = prep["dropmask"], prep["ready"]
+        if not ready:
             dm = K.dropmask_buffer(B, H, Lq, Lk, dh, C.p, q.device)
         S["dropmask"] = dm
         # training: the O rounding residual keeps the backward's delta exact (see include/asrx.h o_lo)
@@ -290,12 +305,133 @@ def attn_bwd(C, S, q, k, v, o, do, dq, dk, dv, gstrides):
 
 # ------------------------------------------------------------------------------------------------ sublayers
 
-def ln_fwd_attn(C, x, ln, prep, B, H, Lq, Lk, dh, on=True):
+def _resolved(w):
+    return w
+
+
+def _strides(ts, Ls):
+    """(row stride, batch stride) of each attention operand, read off the tensor: [B*L, ld] rows (any column
+    slice of a wider matrix), or a [B, P >= L, ld] cache of which L positions are in use."""
+    return tuple((t.stride(1), t.stride(0)) if t.dim() == 3 else (t.stride(0), L * t.stride(0))
+                 for t, L in zip(ts, Ls))
+
+
+def attn_core_fwd(C, w, xq, B, H, dh, Lq, Lk, spec, xk=None, kv=None, kv_dst=None, resid=None, prep=None,
+                  wcast=_resolved):
+    """Drop(W_o attn(q, k, v) + b_o) (+ resid), fp32 [B*Lq, d], for H heads of width dh (n = H*dh concatenated).
+    w = (Wq, bq, Wkv, bkv, Wo, bo); xq [B*Lq, d] (and xk [B*Lk, d]) in the compute dtype.  The projections are
+    * xk and kv None: one GEMM of xq with Wq = the fused [3n, d] q | k | v weight;
+    * xk given: q from xq, k | v from xk with Wkv — into a fresh [B*Lk, 2n], or, where the attention reads a cache
+      `kv`, into kv_dst, the view of the cache rows that xk holds;
+    * only kv given: q from xq; k | v are the already projected columns of kv.
+    wcast turns a weight into the GEMM operand where it is used (the default: w holds operands already).  The
+    seeds are drawn in the order attention (prep, if the caller drew it earlier), out-projection dropout."""
+    M, d = xq.shape
+    n = H * dh
+    Wq, bq, Wkv, bkv, Wo, bo = w
+    if xk is None and kv is None:
+        q = _empty((M, 3 * n), C.cd, xq)
+        K.linear(xq, wcast(Wq), q, bias=bq)
+        kv = q[:, n:]
+    else:
+        q = _empty((M, n), C.cd, xq)
+        K.linear(xq, wcast(Wq), q, bias=bq)
+        if xk is not None:
+            if kv is None:
+                kv = kv_dst = _empty((B * Lk, 2 * n), C.cd, xq)
+            K.linear(xk, wcast(Wkv), kv_dst, bias=bkv)
+    v = kv[..., n:]
+    o = _empty((M, n), C.cd, xq)
+    A = attn_fwd(C, q, kv, v, o, B, H, Lq, Lk, dh, _strides((q, kv, v, o), (Lq, Lk, Lk, Lq)), d ** -0.5, spec, prep)
+    y = _empty((M, d), torch.float32, xq)
+    sd = C.seed()
+    K.linear(o, wcast(Wo), y, bias=bo, dropout_p=C.p, seed=sd, resid=resid, ld_resid=d)
+    return y, dict(xq=xq, xk=xk, q=q, kv=kv, o=o, A=A, sd=sd)
+
+
+def attn_core_bwd(C, S, w, dy_c, sink, dx_dtype, dkv=None, dres=None, sum_dk=False, wcast=_resolved):
+    """Backward of attn_core_fwd from dy_c = dropout_bwd of the output gradient (compute dtype).
+    w = ((Wq, *gq), (Wkv, *gkv) or None, (Wo, *go)): each weight with what sink(dy, x, *g) needs to place dW, db
+    (Ctx.wgrad: the flat store's gradient views; else whatever returns fresh gradients to autograd).
+    dkv: where dK | dV go when K | V were handed in projected.  dres: fp32 residual gradient added to dx.
+    sum_dk: xk was xq, so dx += dk_in.  Returns dx (dx_dtype), dk_in (fp32, None without xk) and the sink's
+    results in launch order (out-projection, q [| k | v], k | v)."""
+    xq, xk, q, kv, o, A = S["xq"], S["xk"], S["q"], S["kv"], S["o"], S["A"]
+    B, H, Lq, Lk, dh = A["dims"]
+    M, d = xq.shape
+    n = H * dh
+    (Wq, *gq), wkv, (Wo, *go) = w
+    do = _empty((M, n), C.cd, xq)
+    K.linear_dgrad(dy_c, wcast(Wo), do)
+    grads = [sink(dy_c, o, *go)]
+    dq = _empty(q.shape, C.cd, xq)
+    if q.shape[1] == 3 * n:
+        dkv = dq[:, n:]
+    elif dkv is None:
+        dkv = _empty((B * Lk, 2 * n), C.cd, xq)
+    dv = dkv[..., n:]
+    attn_bwd(C, A, q, kv, kv[..., n:], o, do, dq, dkv, dv, _strides((do, dq, dkv, dv), (Lq, Lq, Lk, Lk)))
+    dx = _empty((M, d), dx_dtype, xq)
+    K.linear_dgrad(dq, wcast(Wq), dx)
+    grads.append(sink(dq, xq, *gq))
+    if dres is not None:
+        K.ewise(K.EW_ADD, dx, dx, b=dres)
+    dk_in = None
+    if xk is not None:
+        Wkv, *gkv = wkv
+        dk_in = _empty((B * Lk, d), torch.float32, xq)
+        K.linear_dgrad(dkv, wcast(Wkv), dk_in)
+        grads.append(sink(dkv, xk, *gkv))
+        if sum_dk:
+            K.ewise(K.EW_ADD, dx, dx, b=dk_in)
+    return dx, dk_in, grads
+
+
+def ffn_core_fwd(C, w, x, resid=None, bits=False, wcast=_resolved):
+    """W2 Drop(ReLU(W1 x + b1)) + b2 (+ resid), fp32; w = (W1, b1, W2, b2), x in the compute dtype.  bits: keep
+    the 1-bit mask f > 0 (ReLU and dropout keep) that the first GEMM's epilogue can also write, as the data
+    gradient's gate — M*nf/8 bytes instead of the 2*M*nf of f itself (training in bf16, nf % 32 == 0: only the
+    backward reads them).  Returns y, f, the bits or None."""
+    W1, b1, W2, b2 = w
+    M, nf, d = x.shape[0], W1.shape[0], W2.shape[0]
+    f = _empty((M, nf), C.cd, x)
+    sf = C.seed()
+    fb = None
+    if bits and C.train and C.cd == torch.bfloat16 and nf % 32 == 0:
+        fb = _empty((M, nf // 32), torch.int32, x)
+    K.linear(x, wcast(W1), f, bias=b1, relu=True, dropout_p=C.p, seed=sf, mask_out=fb, ld_mask=nf // 32)
+    y = _empty((M, d), torch.float32, x)
+    K.linear(f, wcast(W2), y, bias=b2, resid=resid, ld_resid=d)
+    return y, f, fb
+
+
+def ffn_core_bwd(C, w, x, f, fb, dy_c, sink, dx_dtype, dres=None, wcast=_resolved):
+    """Backward of ffn_core_fwd; w = ((W1, *g1), (W2, *g2)), sink / dres / the returns as in attn_core_bwd (the
+    sink's results: W2's, then W1's)."""
+    (W1, *g1), (W2, *g2) = w
+    M, nf = f.shape
+    dpre = _empty((M, nf), C.cd, x)
+    keep_scale = 1.0 / (1.0 - C.p) if C.p > 0 else 1.0
+    # f = Drop(ReLU(pre)) -> dpre = df * [f > 0] / (1-p)   (f > 0 <=> pre > 0 and kept)
+    if fb is not None:
+        K.linear_dgrad(dy_c, wcast(W2), dpre, alpha=keep_scale, gate=fb, ld_gate=nf // 32, gate_bits=True)
+    else:
+        K.linear_dgrad(dy_c, wcast(W2), dpre, alpha=keep_scale, gate=f, ld_gate=nf)
+    grads = [sink(dy_c, f, *g2)]
+    dx = _empty((M, W1.shape[1]), dx_dtype, x)
+    K.linear_dgrad(dpre, wcast(W1), dx)
+    grads.append(sink(dpre, x, *g1))
+    if dres is not None:
+        K.ewise(K.EW_ADD, dx, dx, b=dres)
+    return dx, grads
+
+
+def ln_fwd_attn(C, x, ln, prep, B, H, Lq, Lk, dh):
     """The sublayer's LayerNorm; where the fused attention will take dropout keep bits, they are generated in the
     same launch (asrx_layernorm_fwd_attn_dropgen) and handed to the attention through prep."""
     d = x.shape[1]
     dm = (K.dropmask_buffer(B, H, Lq, Lk, dh, C.p, x.device)
-          if on and LN_DROPGEN and prep["dropmask"] is None and C.cd == torch.bfloat16 and C.attn_impl == "fused"
+          if prep["dropmask"] is None and C.cd == torch.bfloat16 and C.attn_impl == "fused"
           and d == 512 and x.dtype == torch.float32 else None)
     if dm is None:
         return ln_fwd(C, x, ln)
@@ -305,119 +441,78 @@ def ln_fwd_attn(C, x, ln, prep, B, H, Lq, Lk, dh, on=True):
     return h, mean, rstd
 
 
+def _out_w(C, mha):
+    out = mha._out_linear
+    return C.W(out.weight), C.G(out.weight), C.G(out.bias)
+
+
+def _sublayer_bwd(C, S, dh, dy, dx_c_out, dx_c_p, dx_c_seed):
+    """Through the sublayer's LayerNorm: dx (fp32) = LN^T dh + dy; dx_c_out = dropout_bwd(dx) for the one below."""
+    return ln_bwd(C, S["x"], dh, S["ln"], S["mean"], S["rstd"], dres=dy, drop_out=dx_c_out, drop_seed=dx_c_seed,
+                  drop_p=dx_c_p)
+
+
 def self_attn_fwd(C, x, ln, mha, B, T, H, spec):
     """x + Drop(MHA(LN(x))) with fused per-head projections (layers.py:10-12 -> one N=3d GEMM)."""
-    M, d = x.shape
-    dh = d // H
-    prep = attn_prepare(C, B, H, T, T, dh, x.device)
+    dh = x.shape[1] // H
+    prep = attn_prepare(C)
     h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, T, T, dh)
-    qkv = _empty((M, 3 * d), C.cd, x)
-    K.linear(h, C.W(mha.wqkv), qkv, bias=mha.bqkv.data)
-    o = _empty((M, d), C.cd, x)
-    st = ((3 * d, T * 3 * d),) * 3 + ((d, T * d),)
-    A = attn_fwd(C, qkv, qkv[:, d:], qkv[:, 2 * d:], o, B, H, T, T, dh, st, d ** -0.5, spec, prep)
-    y = _empty((M, d), torch.float32, x)
-    sd = C.seed()
-    K.linear(o, C.W(mha._out_linear.weight), y, bias=mha._out_linear.bias.data, dropout_p=C.p, seed=sd, resid=x,
-             ld_resid=d)
-    return y, dict(x=x, h=h, mean=mean, rstd=rstd, qkv=qkv, o=o, A=A, sd=sd, ln=ln, mha=mha, H=H, T=T, B=B)
+    w = (C.W(mha.wqkv), mha.bqkv.data, None, None, C.W(mha._out_linear.weight), mha._out_linear.bias.data)
+    y, S = attn_core_fwd(C, w, h, B, H, dh, T, T, spec, resid=x, prep=prep)
+    S.update(x=x, mean=mean, rstd=rstd, ln=ln, mha=mha)
+    return y, S
 
 
 def self_attn_bwd(C, S, dy, dy_c, dx_c_out=None, dx_c_p=0.0, dx_c_seed=0):
     """dy: fp32 grad of the sublayer output; dy_c: dropout_bwd(dy) in the compute dtype (out-proj dY).
     Returns dx (fp32) and fills dx_c_out (compute dtype) = dropout_bwd of dx for the sublayer below."""
-    x, h, qkv, o, mha = S["x"], S["h"], S["qkv"], S["o"], S["mha"]
-    M, d = x.shape
-    T, B = S["T"], S["B"]
-    W, G = C.W, C.G
-    do = _empty((M, d), C.cd, x)
-    K.linear_dgrad(dy_c, W(mha._out_linear.weight), do)
-    C.wgrad(dy_c, o, G(mha._out_linear.weight), G(mha._out_linear.bias))
-    dqkv = _empty((M, 3 * d), C.cd, x)
-    gst = ((d, T * d),) + ((3 * d, T * 3 * d),) * 3
-    attn_bwd(C, S["A"], qkv, qkv[:, d:], qkv[:, 2 * d:], o, do, dqkv, dqkv[:, d:], dqkv[:, 2 * d:], gst)
-    dh = _empty((M, d), C.cd, x)
-    K.linear_dgrad(dqkv, W(mha.wqkv), dh)
-    C.wgrad(dqkv, h, G(mha.wqkv), G(mha.bqkv))
-    return ln_bwd(C, x, dh, S["ln"], S["mean"], S["rstd"], dres=dy, drop_out=dx_c_out, drop_seed=dx_c_seed,
-                  drop_p=dx_c_p)
+    mha = S["mha"]
+    w = ((C.W(mha.wqkv), C.G(mha.wqkv), C.G(mha.bqkv)), None, _out_w(C, mha))
+    dh, _, _ = attn_core_bwd(C, S, w, dy_c, C.wgrad, C.cd)
+    return _sublayer_bwd(C, S, dh, dy, dx_c_out, dx_c_p, dx_c_seed)
 
 
 def cross_attn_fwd(C, x, ln, mha, kv, kv_ld, B, L, Te, H):
-    """x + Drop(MHA(LN(x), enc)) — no mask (model.py:71); K/V come from the precomputed all-layer projection."""
-    M, d = x.shape
-    dh = d // H
-    prep = attn_prepare(C, B, H, L, Te, dh, x.device)
-    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, L, Te, dh, on=LN_DROPGEN_CROSS)
-    q = _empty((M, d), C.cd, x)
-    K.linear(h, C.W(mha.wq), q, bias=mha.bq.data)
-    o = _empty((M, d), C.cd, x)
-    st = ((d, L * d), (kv_ld, Te * kv_ld), (kv_ld, Te * kv_ld), (d, L * d))
-    A = attn_fwd(C, q, kv, kv[:, d:], o, B, H, L, Te, dh, st, d ** -0.5, MaskSpec(), prep)
-    y = _empty((M, d), torch.float32, x)
-    sd = C.seed()
-    K.linear(o, C.W(mha._out_linear.weight), y, bias=mha._out_linear.bias.data, dropout_p=C.p, seed=sd, resid=x,
-             ld_resid=d)
-    return y, dict(x=x, h=h, mean=mean, rstd=rstd, q=q, o=o, A=A, sd=sd, ln=ln, mha=mha, L=L, Te=Te, kv=kv,
-                   kv_ld=kv_ld)
+    """x + Drop(MHA(LN(x), enc)) — no mask (model.py:71); K/V come from the precomputed all-layer projection
+    (kv: this layer's columns of it, kv_ld its row stride)."""
+    assert kv.stride(0) == kv_ld
+    dh = x.shape[1] // H
+    prep = attn_prepare(C)
+    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, L, Te, dh)
+    w = (C.W(mha.wq), mha.bq.data, None, None, C.W(mha._out_linear.weight), mha._out_linear.bias.data)
+    y, S = attn_core_fwd(C, w, h, B, H, dh, L, Te, MaskSpec(), kv=kv, resid=x, prep=prep)
+    S.update(x=x, mean=mean, rstd=rstd, ln=ln, mha=mha)
+    return y, S
 
 
 def cross_attn_bwd(C, S, dy, dy_c, dkv, dx_c_out=None, dx_c_p=0.0, dx_c_seed=0):
-    x, h, q, o, mha, kv, kv_ld = S["x"], S["h"], S["q"], S["o"], S["mha"], S["kv"], S["kv_ld"]
-    M, d = x.shape
-    L, Te = S["L"], S["Te"]
-    W, G = C.W, C.G
-    do = _empty((M, d), C.cd, x)
-    K.linear_dgrad(dy_c, W(mha._out_linear.weight), do)
-    C.wgrad(dy_c, o, G(mha._out_linear.weight), G(mha._out_linear.bias))
-    dq = _empty((M, d), C.cd, x)
-    gst = ((d, L * d), (d, L * d), (kv_ld, Te * kv_ld), (kv_ld, Te * kv_ld))
-    attn_bwd(C, S["A"], q, kv, kv[:, d:], o, do, dq, dkv, dkv[:, d:], gst)
-    dh = _empty((M, d), C.cd, x)
-    K.linear_dgrad(dq, W(mha.wq), dh)
-    C.wgrad(dq, h, G(mha.wq), G(mha.bq))
-    return ln_bwd(C, x, dh, S["ln"], S["mean"], S["rstd"], dres=dy, drop_out=dx_c_out, drop_seed=dx_c_seed,
-                  drop_p=dx_c_p)
+    mha = S["mha"]
+    w = ((C.W(mha.wq), C.G(mha.wq), C.G(mha.bq)), None, _out_w(C, mha))
+    dh, _, _ = attn_core_bwd(C, S, w, dy_c, C.wgrad, C.cd, dkv=dkv)
+    return _sublayer_bwd(C, S, dh, dy, dx_c_out, dx_c_p, dx_c_seed)
+
+
+def ffn_w_fwd(C, ff):
+    """A FeedForward's weights in the flat store, as ffn_core_fwd takes them."""
+    return C.W(ff.squeeze.weight), ff.squeeze.bias.data, C.W(ff.unsqueeze.weight), ff.unsqueeze.bias.data
+
+
+def ffn_w_bwd(C, ff):
+    """... and as ffn_core_bwd takes them, with the gradient views for Ctx.wgrad."""
+    return ((C.W(ff.squeeze.weight), C.G(ff.squeeze.weight), C.G(ff.squeeze.bias)),
+            (C.W(ff.unsqueeze.weight), C.G(ff.unsqueeze.weight), C.G(ff.unsqueeze.bias)))
 
 
 def ffn_fwd(C, x, ln, ff):
     """x + W2 Drop(ReLU(W1 LN(x) + b1)) + b2 (layers.py:53-58; residual model.py:24,74)."""
-    M, d = x.shape
     h, mean, rstd = ln_fwd(C, x, ln)
-    nf = ff.squeeze.weight.shape[0]
-    f = _empty((M, nf), C.cd, x)
-    sf = C.seed()
-    # bf16: the epilogue also writes the 1-bit mask f > 0 (ReLU and dropout keep), which the data gradient
-    # reads as its gate: M*nf/8 bytes instead of the 2*M*nf of f itself
-    fb = None
-    if C.train and C.cd == torch.bfloat16 and nf % 32 == 0 and GATE_BITS:   # (only the backward reads them)
-        fb = _empty((M, nf // 32), torch.int32, x)
-    K.linear(h, C.W(ff.squeeze.weight), f, bias=ff.squeeze.bias.data, relu=True, dropout_p=C.p, seed=sf,
-             mask_out=fb, ld_mask=nf // 32)
-    y = _empty((M, d), torch.float32, x)
-    K.linear(f, C.W(ff.unsqueeze.weight), y, bias=ff.unsqueeze.bias.data, resid=x, ld_resid=d)
+    y, f, fb = ffn_core_fwd(C, ffn_w_fwd(C, ff), h, resid=x, bits=True)
     return y, dict(x=x, h=h, mean=mean, rstd=rstd, f=f, fb=fb, ln=ln, ff=ff)
 
 
 def ffn_bwd(C, S, dy, dy_c, dx_c_out=None, dx_c_p=0.0, dx_c_seed=0):
-    x, h, f, ff = S["x"], S["h"], S["f"], S["ff"]
-    M, d = x.shape
-    nf = f.shape[1]
-    W, G = C.W, C.G
-    dpre = _empty((M, nf), C.cd, x)
-    keep_scale = 1.0 / (1.0 - C.p) if C.p > 0 else 1.0
-    # f = Drop(ReLU(pre)) -> dpre = df * [f > 0] / (1-p)   (f > 0 <=> pre > 0 and kept)
-    if S.get("fb") is not None:
-        K.linear_dgrad(dy_c, W(ff.unsqueeze.weight), dpre, alpha=keep_scale, gate=S["fb"], ld_gate=nf // 32,
-                       gate_bits=True)
-    else:
-        K.linear_dgrad(dy_c, W(ff.unsqueeze.weight), dpre, alpha=keep_scale, gate=f, ld_gate=nf)
-    C.wgrad(dy_c, f, G(ff.unsqueeze.weight), G(ff.unsqueeze.bias))
-    dh = _empty((M, d), C.cd, x)
-    K.linear_dgrad(dpre, W(ff.squeeze.weight), dh)
-    C.wgrad(dpre, h, G(ff.squeeze.weight), G(ff.squeeze.bias))
-    return ln_bwd(C, x, dh, S["ln"], S["mean"], S["rstd"], dres=dy, drop_out=dx_c_out, drop_seed=dx_c_seed,
-                  drop_p=dx_c_p)
+    dh, _ = ffn_core_bwd(C, ffn_w_bwd(C, S["ff"]), S["h"], S["f"], S["fb"], dy_c, C.wgrad, C.cd)
+    return _sublayer_bwd(C, S, dh, dy, dx_c_out, dx_c_p, dx_c_seed)
 
 
 # ------------------------------------------------------------------------------------------------ layers

@@ -510,43 +510,45 @@ def _decoder_evaluate_recompute(dec, x, enc_x):
     return decoder_input, probs
 
 
+def _mha_params(m):
+    """(weight, bias, rows) of an MHA's q, k | v and out projections; in self-attention the first two are row
+    blocks of the fused q | k | v weight."""
+    out = m._out_linear
+    d = out.weight.shape[0]
+    if m.cross:
+        qkv = [(m.wq, m.bq, slice(None)), (m.wkv, m.bkv, slice(None))]
+    else:
+        qkv = [(m.wqkv, m.bqkv, slice(0, d)), (m.wqkv, m.bqkv, slice(d, None))]
+    return qkv + [(out.weight, out.bias, slice(None))]
+
+
+def _mha_fwd_w(C, m):
+    """(Wq, bq, Wkv, bkv, Wo, bo) of Bk.attn_core_fwd with separate q and k | v projections."""
+    return sum(((C.W(p)[r], b.data[r]) for p, b, r in _mha_params(m)), ())
+
+
 def _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te):
     """One decoder position for B samples x W hypotheses (rows b*W + w): the embedding of `cur` at position t through
     every layer (pe = the positional table), returning the fp32 stream [B*W, d].  kvs [n][B*W][P][2d] are the
     self-attention K/V caches, which gain position t; kvx [B*Te][n*2d] holds every layer's cross-attention K/V per
     SAMPLE: the W hypotheses of a sample share it, so cross-attention runs as batch = B with W queries each (W = 1:
     greedy decoding)."""
-    dev = cur.device
-    d, H, n = dec.emb_dim, dec.num_heads, len(dec._layers)
+    d, H = dec.emb_dim, dec.num_heads
     dh = d // H
-    R, P = B * W, kvs.shape[2]
-    scale = d ** -0.5
-    xs = torch.empty(R, d, dtype=torch.float32, device=dev)
+    R = B * W
+    none = MaskSpec()
+    xs = torch.empty(R, d, dtype=torch.float32, device=cur.device)
     K.embed_fwd(cur, dec._embedding.weight.data, pe[t:t + 1], xs, 1)
     for l, layer in enumerate(dec._layers):
         mha, cr = layer._mask_attention, layer._cross_attention
         # masked self-attention: the new position's K/V join the cache, its query attends to positions 0..t
         h, _, _ = Bk.ln_fwd(C, xs, layer._norm1)
-        q = torch.empty(R, d, dtype=C.cd, device=dev)
-        wqkv, bqkv = C.W(mha.wqkv), mha.bqkv.data
-        K.linear(h, wqkv[:d], q, bias=bqkv[:d])
-        cache = kvs[l]
-        K.gemm(h, wqkv[d:], cache[:, t], R, 2 * d, d, lda=d, ldb=d, ldc=P * 2 * d, bias=bqkv[d:])
-        o = torch.empty(R, d, dtype=C.cd, device=dev)
-        st = ((d, d), (2 * d, P * 2 * d), (2 * d, P * 2 * d), (d, d))
-        Bk.attn_fwd(C, q, cache, cache[:, :, d:], o, R, H, 1, t + 1, dh, st, scale, MaskSpec())
-        x1 = torch.empty(R, d, dtype=torch.float32, device=dev)
-        K.linear(o, C.W(mha._out_linear.weight), x1, bias=mha._out_linear.bias.data, resid=xs, ld_resid=d)
+        x1, _ = Bk.attn_core_fwd(C, _mha_fwd_w(C, mha), h, R, H, dh, 1, t + 1, none, xk=h, kv=kvs[l],
+                                 kv_dst=kvs[l][:, t], resid=xs)
         # cross-attention over the encoder output (no mask, model.py:71)
         h2, _, _ = Bk.ln_fwd(C, x1, layer._norm2)
-        q2 = torch.empty(R, d, dtype=C.cd, device=dev)
-        K.linear(h2, C.W(cr.wq), q2, bias=cr.bq.data)
-        o2 = torch.empty(R, d, dtype=C.cd, device=dev)
-        kv_l = kvx[:, l * 2 * d:]
-        st2 = ((d, W * d), (n * 2 * d, Te * n * 2 * d), (n * 2 * d, Te * n * 2 * d), (d, W * d))
-        Bk.attn_fwd(C, q2, kv_l, kv_l[:, d:], o2, B, H, W, Te, dh, st2, scale, MaskSpec())
-        x2 = torch.empty(R, d, dtype=torch.float32, device=dev)
-        K.linear(o2, C.W(cr._out_linear.weight), x2, bias=cr._out_linear.bias.data, resid=x1, ld_resid=d)
+        w = (C.W(cr.wq), cr.bq.data, None, None, C.W(cr._out_linear.weight), cr._out_linear.bias.data)
+        x2, _ = Bk.attn_core_fwd(C, w, h2, B, H, dh, W, Te, none, kv=kvx[:, l * 2 * d:], resid=x1)
         xs, _ = Bk.ffn_fwd(C, x2, layer._norm3, layer._feedforward)
     return xs
 
@@ -776,82 +778,30 @@ class _MHAFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, m, C, x, enc_x, attention_mask, *params):
         B, Lq, d = x.shape
-        kv_in = x if enc_x is None else enc_x
-        Lk = kv_in.shape[1]
+        Lk = Lq if enc_x is None else enc_x.shape[1]
         H = m.num_heads
-        dh = d // H
         xc = _cd_input(C, x)
         kc = xc if enc_x is None else _cd_input(C, enc_x)
-        if m.cross:
-            Wq, bq, Wkv, bkv = C.W(m.wq), m.bq.data, C.W(m.wkv), m.bkv.data
-        else:
-            Wq = C.W(m.wqkv)[:d]
-            bq = m.bqkv.data[:d]
-            Wkv, bkv = C.W(m.wqkv)[d:], m.bqkv.data[d:]
-        q = torch.empty(B * Lq, d, dtype=C.cd, device=xc.device)
-        K.linear(xc, Wq, q, bias=bq)
-        kv = torch.empty(B * Lk, 2 * d, dtype=C.cd, device=xc.device)
-        K.linear(kc, Wkv, kv, bias=bkv)
         spec = MaskSpec.from_attention_mask(attention_mask.to(xc.device) if attention_mask is not None else None,
                                             B, Lq, Lk)
-        o = torch.empty(B * Lq, d, dtype=C.cd, device=xc.device)
-        st = ((d, Lq * d), (2 * d, Lk * 2 * d), (2 * d, Lk * 2 * d), (d, Lq * d))
-        A = Bk.attn_fwd(C, q, kv, kv[:, d:], o, B, H, Lq, Lk, dh, st, d ** -0.5, spec)
-        y = torch.empty(B * Lq, d, dtype=torch.float32, device=xc.device)
-        sd = C.seed()
-        K.linear(o, C.W(m._out_linear.weight), y, bias=m._out_linear.bias.data, dropout_p=C.p, seed=sd)
-        ctx.m, ctx.C = m, C
-        ctx.S = dict(xc=xc, kc=kc, q=q, kv=kv, o=o, A=A, sd=sd, dims=(B, Lq, Lk, d), self_attn=enc_x is None,
-                     xdtype=x.dtype, kdtype=kv_in.dtype)
+        y, S = Bk.attn_core_fwd(C, _mha_fwd_w(C, m), xc, B, H, d // H, Lq, Lk, spec, xk=kc)
+        ctx.m, ctx.C, ctx.S = m, C, S
+        ctx.io = (enc_x is None, x.dtype, (x if enc_x is None else enc_x).dtype, Lk)
         return y.view(B, Lq, d).to(x.dtype) if x.dtype != torch.float32 else y.view(B, Lq, d)
 
     @staticmethod
     def backward(ctx, g):
         C, S, m = ctx.C, ctx.S, ctx.m
         _prepare_grads(C)
-        B, Lq, Lk, d = S["dims"]
-        dev = S["xc"].device
+        B, Lq, d = g.shape
+        self_attn, xdtype, kdtype, Lk = ctx.io
         # dropout bwd of the output (same RNG stream as the forward epilogue)
-        g2 = g.reshape(B * Lq, d).contiguous()
-        dy_c = torch.empty(B * Lq, d, dtype=C.cd, device=dev)
-        if C.p > 0:   # the forward epilogue's element mask (same seed), scaled, cast to the compute dtype
-            K.ewise(K.EW_DROPOUT, g2, dy_c, p=C.p, seed=S["sd"])
-        else:
-            K.cast(g2, dy_c)
-        do = torch.empty(B * Lq, d, dtype=C.cd, device=dev)
-        K.linear_dgrad(dy_c, C.W(m._out_linear.weight), do)
-        K.linear_wgrad(dy_c, S["o"], C.G(m._out_linear.weight), bias_grad=C.G(m._out_linear.bias))
-        dq = torch.empty(B * Lq, d, dtype=C.cd, device=dev)
-        dkv = torch.empty(B * Lk, 2 * d, dtype=C.cd, device=dev)
-        q, kv = S["q"], S["kv"]
-        gst = ((d, Lq * d), (d, Lq * d), (2 * d, Lk * 2 * d), (2 * d, Lk * 2 * d))
-        Bk.attn_bwd(C, S["A"], q, kv, kv[:, d:], S["o"], do, dq, dkv, dkv[:, d:], gst)
-        if m.cross:
-            Wq, Wkv, gWq, gbq, gWkv, gbkv = C.W(m.wq), C.W(m.wkv), C.G(m.wq), C.G(m.bq), C.G(m.wkv), C.G(m.bkv)
-        else:
-            Wq, Wkv = C.W(m.wqkv)[:d], C.W(m.wqkv)[d:]
-            gw, gb = C.G(m.wqkv), C.G(m.bqkv)
-            gWq, gbq, gWkv, gbkv = gw[:d], gb[:d], gw[d:], gb[d:]
-        dx = torch.empty(B * Lq, d, dtype=torch.float32, device=dev)
-        K.linear_dgrad(dq, Wq, dx)
-        K.linear_wgrad(dq, S["xc"], gWq, bias_grad=gbq)
-        dk_in = torch.empty(B * Lk, d, dtype=torch.float32, device=dev)
-        K.linear_dgrad(dkv, Wkv, dk_in)
-        K.linear_wgrad(dkv, S["kc"], gWkv, bias_grad=gbkv)
-        if S["self_attn"]:
-            K.ewise(K.EW_ADD, dx, dx, b=dk_in)
-            return (None, None, _as_dtype(dx.view(B, Lq, d), S["xdtype"]), None, None) + (None,) * len(_params(m))
-        return (None, None, _as_dtype(dx.view(B, Lq, d), S["xdtype"]), _as_dtype(dk_in.view(B, Lk, d), S["kdtype"]),
-                None) + (None,) * len(_params(m))
-
-
-def _as_dtype(t, dtype):
-    """t in `dtype` (the caller's input dtype): the native cast kernel when it differs."""
-    if t.dtype == dtype:
-        return t
-    out = torch.empty(t.shape, dtype=dtype, device=t.device)
-    K.cast(t.contiguous(), out)
-    return out
+        dy_c = Bk.drop_bwd_c(C, g.reshape(B * Lq, d).contiguous(), S["sd"])
+        w = [(C.W(p)[r], C.G(p)[r], C.G(b)[r]) for p, b, r in _mha_params(m)]
+        dx, dk_in, _ = Bk.attn_core_bwd(C, S, w, dy_c, C.wgrad, torch.float32, sum_dk=self_attn)
+        dx = Bk.as_dtype(dx.view(B, Lq, d), xdtype)
+        dk = None if self_attn else Bk.as_dtype(dk_in.view(B, Lk, d), kdtype)
+        return (None, None, dx, dk, None) + (None,) * len(_params(m))
 
 
 def mha(m, x, enc_x=None, attention_mask=None):
@@ -864,33 +814,18 @@ class _FFNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ff, C, x, *params):
-        shape = x.shape
         xc = _cd_input(C, x)
-        M = xc.shape[0]
-        nf = ff.ff_dim
-        f = torch.empty(M, nf, dtype=C.cd, device=xc.device)
-        sf = C.seed()
-        K.linear(xc, C.W(ff.squeeze.weight), f, bias=ff.squeeze.bias.data, relu=True, dropout_p=C.p, seed=sf)
-        y = torch.empty(M, ff.emb_dim, dtype=torch.float32, device=xc.device)
-        K.linear(f, C.W(ff.unsqueeze.weight), y, bias=ff.unsqueeze.bias.data)
-        ctx.ff, ctx.C, ctx.S = ff, C, (xc, f, shape, x.dtype)
-        return y.view(shape).to(x.dtype)
+        y, f, _ = Bk.ffn_core_fwd(C, Bk.ffn_w_fwd(C, ff), xc)
+        ctx.ff, ctx.C, ctx.S = ff, C, (xc, f, x.shape, x.dtype)
+        return y.view(x.shape).to(x.dtype)
 
     @staticmethod
     def backward(ctx, g):
         C, ff = ctx.C, ctx.ff
         _prepare_grads(C)
         xc, f, shape, xdt = ctx.S
-        M = xc.shape[0]
-        g2 = g.reshape(M, -1).float().contiguous()
-        g_c = g2.to(C.cd)
-        dpre = torch.empty(M, ff.ff_dim, dtype=C.cd, device=xc.device)
-        K.linear_dgrad(g_c, C.W(ff.unsqueeze.weight), dpre, alpha=1.0 / (1.0 - C.p) if C.p > 0 else 1.0, gate=f,
-                       ld_gate=ff.ff_dim)
-        K.linear_wgrad(g_c, f, C.G(ff.unsqueeze.weight), bias_grad=C.G(ff.unsqueeze.bias))
-        dx = torch.empty(M, ff.emb_dim, dtype=torch.float32, device=xc.device)
-        K.linear_dgrad(dpre, C.W(ff.squeeze.weight), dx)
-        K.linear_wgrad(dpre, xc, C.G(ff.squeeze.weight), bias_grad=C.G(ff.squeeze.bias))
+        g_c = g.reshape(xc.shape[0], -1).float().contiguous().to(C.cd)
+        dx, _ = Bk.ffn_core_bwd(C, Bk.ffn_w_bwd(C, ff), xc, f, None, g_c, C.wgrad, torch.float32)
         return (None, None, dx.view(shape).to(xdt)) + (None,) * len(_params(ff))
 
 

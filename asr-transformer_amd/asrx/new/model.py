@@ -235,8 +235,7 @@ class Decoder(nn.Module):
         S, H, n, V = self.seq_len, self.num_heads, self.num_layers, self.vocab_size
         hd = H * d
         self._check_len(S)
-        scale = d ** -0.5
-        none = K.MaskSpec()
+        C, none = cfg.ctx, K.MaskSpec()
         enc_c = O._cd(enc_x.reshape(B * Te, d).float().contiguous(), cd)
 
         def ln(x, norm):          # the post-LN of new/model.py:80-89 (non_pad_mask is all ones in evaluate)
@@ -244,20 +243,17 @@ class Decoder(nn.Module):
             K.layernorm_fwd(x, norm.weight.detach(), norm.bias.detach(), y)
             return y
 
-        def attend(q, kv, Lk, ldkv, bstride):   # one query per batch row over Lk keys of kv (K | V columns)
-            o = torch.empty(B, hd, dtype=cd, device=dev)
-            st = ((hd, hd), (ldkv, bstride), (ldkv, bstride), (hd, hd))
-            Bk.attn_fwd(cfg.ctx, q, kv, kv[..., hd:], o, B, H, 1, Lk, d, st, scale, none)
-            return o
-
-        lw = []   # per layer: cast weights, the cross K / V of the encoder output
+        lw = []   # per layer: the cast weights of the three sublayers, the cross K / V of the encoder output
         for layer in self.layers:
-            sa, ca = layer.mask_attention, layer.attention
+            sa, ca, ff = layer.mask_attention, layer.attention, layer.ff
             wq = O._w(ca.wqkv, cd)
             kvx = torch.empty(B * Te, 2 * hd, dtype=cd, device=dev)
             K.linear(enc_c, wq[hd:], kvx, bias=ca.bqkv[hd:].detach())
-            lw.append((O._w(sa.wqkv, cd), O._w(sa.out.weight, cd), wq[:hd], O._w(ca.out.weight, cd), kvx,
-                       O._w(layer.ff.squeeze.weight, cd), O._w(layer.ff.unsqueeze.weight, cd)))
+            wqkv, bqkv = O._w(sa.wqkv, cd), sa.bqkv.detach()
+            lw.append(((wqkv[:hd], bqkv[:hd], wqkv[hd:], bqkv[hd:], O._w(sa.out.weight, cd), sa.out.bias.detach()),
+                       (wq[:hd], ca.bqkv[:hd].detach(), None, None, O._w(ca.out.weight, cd), ca.out.bias.detach()),
+                       (O._w(ff.squeeze.weight, cd), ff.squeeze.bias.detach(),
+                        O._w(ff.unsqueeze.weight, cd), ff.unsqueeze.bias.detach()), kvx))
         wcls = O._w(self.classifier.weight, cd)
         caches = torch.empty(n, B, S, 2 * hd, dtype=cd, device=dev)
         logits = torch.empty(B, S, V, dtype=torch.float32, device=dev)
@@ -268,32 +264,17 @@ class Decoder(nn.Module):
         for t in range(S):
             x = torch.empty(B, d, dtype=torch.float32, device=dev)
             K.embed_fwd(cur, self.emb.weight.detach(), pe[t:t + 1].contiguous(), x, 1)   # (eval: no dropout)
-            for l, layer in enumerate(self.layers):
-                wqkv, wo, wq2, wo2, kvx, w1, w2 = lw[l]
-                sa, ca, ff = layer.mask_attention, layer.attention, layer.ff
+            for layer, cache, (w_self, w_cross, w_ff, kvx) in zip(self.layers, caches, lw):
                 # masked self-attention: the new position's K / V into the cache, its query over positions 0..t
                 xc = O._cd(x, cd)
-                q = torch.empty(B, hd, dtype=cd, device=dev)
-                K.linear(xc, wqkv[:hd], q, bias=sa.bqkv[:hd].detach())
-                cache = caches[l]
-                K.gemm(xc, wqkv[hd:], cache[:, t], B, 2 * hd, d, lda=d, ldb=d, ldc=S * 2 * hd,
-                       bias=sa.bqkv[hd:].detach())
-                o = attend(q, cache, t + 1, 2 * hd, S * 2 * hd)
-                y = torch.empty(B, d, dtype=torch.float32, device=dev)
-                K.linear(o, wo, y, bias=sa.out.bias.detach(), resid=x, ld_resid=d)
+                y, _ = Bk.attn_core_fwd(C, w_self, xc, B, H, d, 1, t + 1, none, xk=xc, kv=cache, kv_dst=cache[:, t],
+                                        resid=x)
                 x1 = ln(y, layer.norm1)
                 # cross-attention over the encoder output (no mask in evaluate, new/model.py:136)
-                q2 = torch.empty(B, hd, dtype=cd, device=dev)
-                K.linear(O._cd(x1, cd), wq2, q2, bias=ca.bqkv[:hd].detach())
-                o2 = attend(q2, kvx, Te, 2 * hd, Te * 2 * hd)
-                y2 = torch.empty(B, d, dtype=torch.float32, device=dev)
-                K.linear(o2, wo2, y2, bias=ca.out.bias.detach(), resid=x1, ld_resid=d)
+                y2, _ = Bk.attn_core_fwd(C, w_cross, O._cd(x1, cd), B, H, d, 1, Te, none, kv=kvx, resid=x1)
                 x2 = ln(y2, layer.norm2)
                 # feed-forward with its residual
-                f = torch.empty(B, w1.shape[0], dtype=cd, device=dev)
-                K.linear(O._cd(x2, cd), w1, f, bias=ff.squeeze.bias.detach(), relu=True)
-                y3 = torch.empty(B, d, dtype=torch.float32, device=dev)
-                K.linear(f, w2, y3, bias=ff.unsqueeze.bias.detach(), resid=x2, ld_resid=d)
+                y3, _, _ = Bk.ffn_core_fwd(C, w_ff, O._cd(x2, cd), resid=x2)
                 x = ln(y3, layer.norm3)
             lg = logits[:, t]
             K.gemm(O._cd(x, cd), wcls, lg, B, V, d, lda=d, ldb=d, ldc=S * V)

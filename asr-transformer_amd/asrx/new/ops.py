@@ -16,13 +16,7 @@ from .. import kernels as K
 from ..kernels import MaskSpec
 
 
-def _cd(x, cd):
-    """x (any float dtype, contiguous 2-D) in the compute dtype — a native cast when it differs."""
-    if x.dtype == cd:
-        return x.contiguous()
-    out = torch.empty(x.shape, dtype=cd, device=x.device)
-    K.cast(x.contiguous(), out)
-    return out
+_cd = Bk.as_dtype    # x (any float dtype, contiguous 2-D) in the compute dtype — a native cast when it differs
 
 
 def _w(W, cd):
@@ -137,68 +131,30 @@ class MHAResFn(torch.autograd.Function):
         cd = cfg.cd
         B, Lq, d = x.shape
         Lk = kv_in.shape[1] if kv_in is not None else Lq
-        H, hd = m.num_heads, m.num_heads * d
         xf = x.reshape(B * Lq, d).contiguous()
         xc = _cd(xf, cd)
-        if kv_in is None:      # Wq / bq: the fused [3 h d, d] q | k | v projection (Wkv, bkv unused)
-            qkv = torch.empty(B * Lq, 3 * hd, dtype=cd, device=x.device)
-            K.linear(xc, _w(Wq, cd), qkv, bias=bq.detach())
-            q, kv, kc = qkv, qkv[:, hd:], None
-            st = ((3 * hd, Lq * 3 * hd),) * 3 + ((hd, Lq * hd),)
-        else:
-            kc = _cd(kv_in.reshape(B * Lk, d), cd)
-            q = torch.empty(B * Lq, hd, dtype=cd, device=x.device)
-            K.linear(xc, _w(Wq, cd), q, bias=bq.detach())
-            kv = torch.empty(B * Lk, 2 * hd, dtype=cd, device=x.device)
-            K.linear(kc, _w(Wkv, cd), kv, bias=bkv.detach())
-            st = ((hd, Lq * hd), (2 * hd, Lk * 2 * hd), (2 * hd, Lk * 2 * hd), (hd, Lq * hd))
-        o = torch.empty(B * Lq, hd, dtype=cd, device=x.device)
-        A = Bk.attn_fwd(cfg.ctx, q, kv, kv[:, hd:], o, B, H, Lq, Lk, d, st, d ** -0.5, spec)
-        y = torch.empty(B * Lq, d, dtype=torch.float32, device=x.device)
-        sd = cfg.seed()
-        K.linear(o, _w(Wo, cd), y, bias=bo.detach(), dropout_p=cfg.p, seed=sd, resid=xf, ld_resid=d)
-        ctx.cfg, ctx.spec_dims = cfg, (B, Lq, Lk, d, H, hd)
-        ctx.S = dict(xc=xc, kc=kc, q=q, kv=kv, o=o, A=A, sd=sd, st=st, self_attn=kv_in is None)
+        # self-attention: Wq / bq are the fused [3 h d, d] q | k | v projection (Wkv, bkv None)
+        kc = _cd(kv_in.reshape(B * Lk, d), cd) if kv_in is not None else None
+        w = (Wq, bq.detach(), Wkv, bkv.detach() if bkv is not None else None, Wo, bo.detach())
+        y, ctx.S = Bk.attn_core_fwd(cfg.ctx, w, xc, B, m.num_heads, d, Lq, Lk, spec, xk=kc, resid=xf,
+                                    wcast=lambda W: _w(W, cd))
+        ctx.cfg = cfg
         ctx.save_for_backward(Wq, bq, Wkv, bkv, Wo, bo)
         return y.view(B, Lq, d)
 
     @staticmethod
     def backward(ctx, g):
-        cfg, S = ctx.cfg, ctx.S
-        cd = cfg.cd
+        cfg = ctx.cfg
         Wq, bq, Wkv, bkv, Wo, bo = ctx.saved_tensors
-        B, Lq, Lk, d, H, hd = ctx.spec_dims
-        dev = g.device
+        B, Lq, d = g.shape
         g2 = g.reshape(B * Lq, d).contiguous().float()
-        dy_c = torch.empty(B * Lq, d, dtype=cd, device=dev)
-        if cfg.p > 0:      # the out-projection epilogue's keep mask (same seed, element index)
-            K.ewise(K.EW_DROPOUT, g2, dy_c, p=cfg.p, seed=S["sd"])
-        else:
-            K.cast(g2, dy_c)
-        do = torch.empty(B * Lq, hd, dtype=cd, device=dev)
-        K.linear_dgrad(dy_c, _w(Wo, cd), do)
-        gWo, gbo = _wgrad(dy_c, S["o"], Wo, bo)
-        q, kv = S["q"], S["kv"]
-        dx = torch.empty(B * Lq, d, dtype=torch.float32, device=dev)
-        if S["self_attn"]:
-            dqkv = torch.empty(B * Lq, 3 * hd, dtype=cd, device=dev)
-            gst = ((hd, Lq * hd),) + ((3 * hd, Lq * 3 * hd),) * 3
-            Bk.attn_bwd(cfg.ctx, S["A"], q, kv, kv[:, hd:], S["o"], do, dqkv, dqkv[:, hd:], dqkv[:, 2 * hd:], gst)
-            K.linear_dgrad(dqkv, _w(Wq, cd), dx)
-            gW, gb = _wgrad(dqkv, S["xc"], Wq, bq)
-            K.ewise(K.EW_ADD, dx, dx, b=g2)          # + the residual
-            return (dx.view(B, Lq, d), None, None, None, None, gW, gb, None, None, gWo, gbo)
-        dq = torch.empty(B * Lq, hd, dtype=cd, device=dev)
-        dkv = torch.empty(B * Lk, 2 * hd, dtype=cd, device=dev)
-        gst = ((hd, Lq * hd), (hd, Lq * hd), (2 * hd, Lk * 2 * hd), (2 * hd, Lk * 2 * hd))
-        Bk.attn_bwd(cfg.ctx, S["A"], q, kv, kv[:, hd:], S["o"], do, dq, dkv, dkv[:, hd:], gst)
-        K.linear_dgrad(dq, _w(Wq, cd), dx)
-        gWq, gbq = _wgrad(dq, S["xc"], Wq, bq)
-        K.ewise(K.EW_ADD, dx, dx, b=g2)
-        dk_in = torch.empty(B * Lk, d, dtype=torch.float32, device=dev)
-        K.linear_dgrad(dkv, _w(Wkv, cd), dk_in)
-        gWkv, gbkv = _wgrad(dkv, S["kc"], Wkv, bkv)
-        return (dx.view(B, Lq, d), dk_in.view(B, Lk, d), None, None, None, gWq, gbq, gWkv, gbkv, gWo, gbo)
+        dy_c = Bk.drop_bwd_c(cfg.ctx, g2, ctx.S["sd"])   # the out-projection epilogue's keep mask
+        w = ((Wq, Wq, bq), (Wkv, Wkv, bkv), (Wo, Wo, bo))
+        dx, dk_in, (go, gq, *gkv) = Bk.attn_core_bwd(cfg.ctx, ctx.S, w, dy_c, _wgrad, torch.float32, dres=g2,
+                                                     wcast=lambda W: _w(W, cfg.cd))
+        if dk_in is None:
+            return (dx.view(B, Lq, d), None, None, None, None, *gq, None, None, *go)
+        return (dx.view(B, Lq, d), dk_in.view(B, -1, d), None, None, None, *gq, *gkv[0], *go)
 
 
 class FFNResFn(torch.autograd.Function):
@@ -212,31 +168,21 @@ class FFNResFn(torch.autograd.Function):
         B, T, d = x.shape
         xf = x.reshape(B * T, d).contiguous()
         xc = _cd(xf, cd)
-        f = torch.empty(B * T, W1.shape[0], dtype=cd, device=x.device)
-        K.linear(xc, _w(W1, cd), f, bias=b1.detach(), relu=True, dropout_p=cfg.p, seed=cfg.seed())
-        y = torch.empty(B * T, d, dtype=torch.float32, device=x.device)
-        K.linear(f, _w(W2, cd), y, bias=b2.detach(), resid=xf, ld_resid=d)
-        ctx.cfg, ctx.shape = cfg, (B, T, d)
+        y, f, _ = Bk.ffn_core_fwd(cfg.ctx, (W1, b1.detach(), W2, b2.detach()), xc, resid=xf,
+                                  wcast=lambda W: _w(W, cd))
+        ctx.cfg = cfg
         ctx.save_for_backward(xc, f, W1, b1, W2, b2)
         return y.view(B, T, d)
 
     @staticmethod
     def backward(ctx, g):
         cfg = ctx.cfg
-        cd = cfg.cd
         xc, f, W1, b1, W2, b2 = ctx.saved_tensors
-        B, T, d = ctx.shape
+        B, T, d = g.shape
         g2 = g.reshape(B * T, d).contiguous().float()
-        gc = _cd(g2, cd)
-        nf = f.shape[1]
-        dpre = torch.empty(B * T, nf, dtype=cd, device=g.device)
-        K.linear_dgrad(gc, _w(W2, cd), dpre, alpha=1.0 / (1.0 - cfg.p) if cfg.p > 0 else 1.0, gate=f, ld_gate=nf)
-        gW2, gb2 = _wgrad(gc, f, W2, b2)
-        dx = torch.empty(B * T, d, dtype=torch.float32, device=g.device)
-        K.linear_dgrad(dpre, _w(W1, cd), dx)
-        gW1, gb1 = _wgrad(dpre, xc, W1, b1)
-        K.ewise(K.EW_ADD, dx, dx, b=g2)
-        return dx.view(B, T, d), None, gW1, gb1, gW2, gb2
+        dx, (g2w, g1w) = Bk.ffn_core_bwd(cfg.ctx, ((W1, W1, b1), (W2, W2, b2)), xc, f, None, _cd(g2, cfg.cd), _wgrad,
+                                         torch.float32, dres=g2, wcast=lambda W: _w(W, cfg.cd))
+        return (dx.view(B, T, d), None, *g1w, *g2w)
 
 
 def valid_spec(valid, causal=False):
