@@ -6,6 +6,7 @@ native library and a GPU.
 """
 from .layers import MHA, FeedForward, LayerNorm, TrainablePositionalEncoding  # noqa: F401
 from .functions import BeamResult  # noqa: F401
+from .ctc import CTCLoss  # noqa: F401
 from .model import Decoder, DecoderLayer, Encoder, EncoderLayer, FrontEnd, Transformer, subsampled  # noqa: F401
 
 __version__ = "0.1.0"

@@ -150,7 +150,16 @@ SIGNATURES = {
     "asrx_rowwise": [c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_vp],
     "asrx_transpose_last2": [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp],
     "asrx_step_tokens": [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
+    "asrx_ctc_loss": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32,
+                      c_vp, c_vp, c_vp, c_i32, c_vp, c_f32, c_f32, c_vp, c_i64, c_vp],
+    "asrx_ctc_targets": [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, ctypes.POINTER(c_i64), c_i32, c_i64, c_vp, c_i64,
+                         c_vp, c_vp],
+    "asrx_ctc_greedy": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp],
+    "asrx_ctc_workspace_elems": [c_i32, c_i32, c_i32],   # (int64 result: lib() rebinds its restype)
 }
+
+CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
+CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended states)
 
 ERRORS = {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}
 
@@ -174,6 +183,8 @@ def lib():
         L.asrx_attn_dropmask_words.restype = c_i64
         L.asrx_attn_dq_acc_elems.argtypes = [c_i32, c_i32, c_i32, c_i32, c_i32]
         L.asrx_attn_dq_acc_elems.restype = c_i64
+        L.asrx_ctc_workspace_elems.argtypes = [c_i32, c_i32, c_i32]
+        L.asrx_ctc_workspace_elems.restype = c_i64
         _lib = L
     return _lib
 

@@ -208,10 +208,11 @@ def release_groups(n, every=None):
     return out
 
 
-def encoder_bwd(C, enc, S, dy, gate_feats, ready=None, release_every=None, carry=None):
+def encoder_bwd(C, enc, S, dy, gate_feats, ready=None, release_every=None, carry=None, with_norm_out=None):
     """dy: grad of the encoder output (fp32 or compute dtype). Returns dfeats (compute dtype).  With `ready`, the
     layers are released to the gradient all-reduce in groups (release_groups; the first with _norm_out) as soon as
-    their gradients are final.  carry: parameters (the decoder's) released with the first group (else at finish)."""
+    their gradients are final.  carry: parameters (the decoder's) released with the first group (else at finish).
+    with_norm_out: further parameters released with _norm_out (the CTC head on the encoder output)."""
     x = S["x"]
     dx_c = torch.empty(x.shape, dtype=C.cd, device=x.device)
     dx = Bk.ln_bwd(C, x, dy, enc._norm_out, S["mean"], S["rstd"], drop_out=dx_c)
@@ -235,7 +236,7 @@ def encoder_bwd(C, enc, S, dy, gate_feats, ready=None, release_every=None, carry
             if i * per + tail <= cus:
                 groups[i] = hi
         if i in groups:
-            extra = list(enc._norm_out.parameters()) if groups[i] == n else []
+            extra = list(enc._norm_out.parameters()) + list(with_norm_out or []) if groups[i] == n else []
             _release(C, ready, [p for l in enc._layers[i:groups[i]] for p in l.parameters()] + extra + (carry or []))
             carry = None
             hi, q0 = i, len(C.wq or [])
@@ -323,9 +324,20 @@ def decoder_bwd(C, dec, S, dlogits_c):
     return denc
 
 
-def model_forward(C, model, spectrum, text, mask, spec=None):
+def ctc_head_fwd(C, model, enc_c):
+    """fp32 CTC logits [B*T', Vp] of the compute-dtype encoder output [B*T', d] (Transformer.ctc_head)."""
+    head = getattr(model, "ctc_head", None)
+    if head is None:
+        raise RuntimeError("asrx: the model has no CTC head (build it with Transformer(..., ctc=True))")
+    logits = torch.empty(enc_c.shape[0], head.Vp, dtype=torch.float32, device=enc_c.device)
+    K.linear(enc_c, C.W(head.weight), logits)
+    return logits
+
+
+def model_forward(C, model, spectrum, text, mask, spec=None, ctc=False):
     """Transformer.forward (model.py:194-198) as one native program. Returns (logits [B*L, Vp] fp32, S).  spec:
-    the decoder's self-attention mask when the caller already built it (mask is then unused)."""
+    the decoder's self-attention mask when the caller already built it (mask is then unused).  ctc: also run the CTC
+    head on the encoder output, S["ctc_logits"] (fp32 [B*T', Vp])."""
     dev = C.store.device
     spectrum = spectrum.to(dev)
     feats, Sf = Bk.frontend_fwd(C, spectrum, model.input_layer[0], model.input_layer[2])
@@ -334,16 +346,30 @@ def model_forward(C, model, spectrum, text, mask, spec=None):
     enc, Se = encoder_fwd(C, model.encoder, feats, B, T2)
     L = text.shape[1]
     logits, Sd = decoder_fwd(C, model.decoder, text, mask, enc, B, L, T2, spec=spec)
-    return logits, dict(f=Sf, e=Se, d=Sd)
+    S = dict(f=Sf, e=Se, d=Sd)
+    if ctc:
+        S["ctc_logits"] = ctc_head_fwd(C, model, enc)
+    return logits, S
 
 
-def model_backward(C, model, S, dlogits_c, ready=None):
+def model_backward(C, model, S, dlogits_c, ready=None, dctc_c=None):
     """Backward of model_forward.  ready(start, end): optional callback that receives flat-gradient ranges as
     they become final (decoder, then upper encoder half) so their all-reduce overlaps the rest of the backward;
-    whatever is not released that way is final when this returns."""
+    whatever is not released that way is final when this returns.  dctc_c: gradient of S["ctc_logits"] ([B*T', Vp]
+    compute dtype, padded columns zero): the head's data gradient is added to the encoder-output gradient before the
+    encoder's backward, its weight gradient joins the queued ones, its range is released with Encoder._norm_out."""
     _prepare_grads(C)
     own = C.defer_wgrad()
     denc = decoder_bwd(C, model.decoder, S["d"], dlogits_c)
+    head_params = None
+    if dctc_c is not None:
+        head = model.ctc_head
+        # denc + dctc . W_head in the GEMM's fp32-residual epilogue (as FFN2 adds its residual stream)
+        dsum = torch.empty_like(denc)
+        K.linear_dgrad(dctc_c, C.W(head.weight), dsum, resid=denc, ld_resid=denc.stride(0))
+        denc = dsum
+        C.wgrad(dctc_c, S["d"]["enc"], C.G(head.weight))
+        head_params = [head.weight]
     # by tile rounds (the default release schedule): the decoder's weight gradients (the 96 long cross K/V tiles and
     # 672 short ones) are not a launch of their own but join the first encoder group's — one ~2-round launch instead
     # of a 313-K-step one plus a 249-K-step one (modelled with kernels.xcd_plan) and one segment boundary fewer;
@@ -353,7 +379,7 @@ def model_backward(C, model, S, dlogits_c, ready=None):
         if not carry:
             _release(C, ready, list(model.decoder.parameters()))
     dfeats = encoder_bwd(C, model.encoder, S["e"], denc, gate_feats=True, ready=ready if own else None,
-                         carry=list(model.decoder.parameters()) if carry else None)
+                         carry=list(model.decoder.parameters()) if carry else None, with_norm_out=head_params)
     Bk.frontend_bwd(C, S["f"], dfeats, model.input_layer[0], model.input_layer[2])
     if own:
         C.flush_wgrad()
@@ -742,6 +768,25 @@ def transformer_evaluate(model, spectrum, text):
     feats = model.input_layer(spectrum)
     enc = model.encoder(feats)
     return model.decoder.evaluate(text, enc)
+
+
+@torch.no_grad()
+def transformer_ctc_logits(model, spectrum):
+    """Front end and encoder as in `evaluate`, then the CTC head: (fp32 logits [B*T', Vp], B, T')."""
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("asrx: the model has no CTC head (build it with Transformer(..., ctc=True))")
+    enc = model.encoder(model.input_layer(spectrum))
+    B, T, d = enc.shape
+    C = make_ctx(model, 0.0)
+    return ctc_head_fwd(C, model, enc.reshape(B * T, d).to(C.cd).contiguous()), B, T
+
+
+@torch.no_grad()
+def transformer_ctc_greedy(model, spectrum, input_lengths=None):
+    logits, B, T = transformer_ctc_logits(model, spectrum)
+    if input_lengths is not None:
+        input_lengths = input_lengths.to(device=logits.device, dtype=torch.int32).contiguous()
+    return K.ctc_greedy(logits, model.ctc_head.V, T, model.ctc_blank, input_lengths)
 
 
 # ------------------------------------------------------------------------------------------- sub-modules

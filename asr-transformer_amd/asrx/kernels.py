@@ -914,6 +914,87 @@ def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_gra
     return loss, dl, am
 
 
+CTC_REDUCTIONS = {"sum": 0, "mean": 1}   # ASRX_CTC_SUM, ASRX_CTC_MEAN
+
+
+def ctc_workspace_elems(B, T, max_target_len):
+    """fp32 workspace elements of ctc_loss (asrx_ctc_workspace_elems: the C-ABI's own size rule)."""
+    from ._lib import lib
+    n = lib().asrx_ctc_workspace_elems(B, T, max_target_len)
+    if n < 0:
+        raise RuntimeError(f"asrx: no CTC workspace for B {B}, T {T}, max target length {max_target_len}")
+    return n
+
+
+def ctc_loss(logits, V, T, targets, target_lengths, input_lengths=None, max_target_len=None, blank=0,
+             reduction="mean", zero_infinity=False, grad_scale=1.0, grad_dtype=torch.bfloat16, want_grad=True,
+             loss_add=None, loss_add_scale=1.0, loss_scale=1.0):
+    """CTC on logits fp32 [B*T, ld] (rows b*T + t, contiguous rows; asrx_ctc_loss, log-softmax fused): targets int64
+    [B, >= max_target_len], target_lengths / input_lengths int32 [B] (input_lengths None = T).  max_target_len is the
+    host-side bound of the lengths (default: the targets' width).  Returns (loss[1] = loss_add_scale * loss_add +
+    loss_scale * reduction, nll fp32 [B], dlogits [B*T, ld] in grad_dtype or None)."""
+    _cuda(logits, targets, target_lengths, input_lengths, loss_add)
+    rows, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
+        "asrx: ctc_loss needs contiguous fp32 logits [B*T, ld]"
+    assert T > 0 and rows % T == 0
+    B = rows // T
+    assert targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[0] == B
+    assert targets.shape[1] == 0 or targets.stride(1) == 1
+    if max_target_len is None:
+        max_target_len = targets.shape[1]
+    assert max_target_len <= targets.shape[1]
+    for a in (target_lengths, input_lengths):
+        assert a is None or (a.dtype == torch.int32 and a.numel() == B and a.is_contiguous())
+    assert loss_add is None or (loss_add.dtype == torch.float32 and loss_add.numel() == 1)
+    dev = logits.device
+    loss = torch.empty(1, device=dev, dtype=torch.float32)
+    nll = torch.empty(B, device=dev, dtype=torch.float32)
+    dl = torch.empty(rows, ld, device=dev, dtype=grad_dtype) if want_grad else None
+    # (the size rule refuses what the call refuses: let the call report a too long target)
+    n = ctc_workspace_elems(B, T, min(max(max_target_len, 0), 255))
+    ws = torch.empty(n, device=dev, dtype=torch.float32)
+    tgt_stride = targets.stride(0) if targets.shape[1] else 0
+    call("asrx_ctc_loss", logits.data_ptr(), B, T, V, ld, targets.data_ptr() if targets.numel() else None, tgt_stride,
+         _p(input_lengths), target_lengths.data_ptr(), max_target_len, blank, CTC_REDUCTIONS[reduction],
+         int(zero_infinity), grad_scale, nll.data_ptr(), loss.data_ptr(), _p(dl), code(dl) if dl is not None else 0,
+         _p(loss_add), loss_add_scale, loss_scale, ws.data_ptr(), n, stream())
+    return loss, nll, dl
+
+
+def ctc_targets(text, mask, drop, blank):
+    """(targets int64 [B, L+1], target_lengths int32 [B]) of a teacher-forced batch (asrx_ctc_targets): per row of
+    `text` (B, L+1) the tokens at positions with mask >= 1 that are none of the (at most four) `drop` ids, left-packed,
+    the tail filled with `blank`."""
+    _cuda(text, mask)
+    assert text.dtype == torch.int64 and mask.dtype == torch.float32 and text.shape == mask.shape and text.dim() == 2
+    assert text.stride(1) == 1 and mask.stride(1) == 1 and len(drop) <= 4
+    B, n = text.shape
+    targets = torch.empty(B, n, dtype=torch.int64, device=text.device)
+    lengths = torch.empty(B, dtype=torch.int32, device=text.device)
+    ids = (ctypes.c_int64 * 4)(*[int(d) for d in drop])
+    call("asrx_ctc_targets", text.data_ptr(), text.stride(0), mask.data_ptr(), mask.stride(0), B, n, ids, len(drop),
+         int(blank), targets.data_ptr(), n, lengths.data_ptr(), stream())
+    return targets, lengths
+
+
+def ctc_greedy(logits, V, T, blank, input_lengths=None):
+    """CTC best path of logits fp32 [B*T, ld] (asrx_ctc_greedy): (tokens int64 [B, T] left-packed, padded with
+    `blank`; lengths int32 [B]).  Frames t >= input_lengths[b] (int32 [B], None = T) are ignored."""
+    _cuda(logits, input_lengths)
+    rows, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld
+    assert T > 0 and rows % T == 0
+    B = rows // T
+    assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == B
+                                     and input_lengths.is_contiguous())
+    tok = torch.empty(B, T, dtype=torch.int64, device=logits.device)
+    lens = torch.empty(B, dtype=torch.int32, device=logits.device)
+    call("asrx_ctc_greedy", logits.data_ptr(), B, T, V, ld, _p(input_lengths), blank, tok.data_ptr(), lens.data_ptr(),
+         stream())
+    return tok, lens
+
+
 def adam(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, decoupled=False, hyp=None):
     """Fused Adam/AdamW step `step` (1-based).  hyp (optional fp32 device [3]): lr and bias corrections read by
     the kernel at run time (a replayed HIP graph; see adam_hyper)."""

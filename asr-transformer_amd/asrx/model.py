@@ -4,7 +4,8 @@ evaluate signatures, same state_dict keys.  Whole stacks run as explicit native 
 (asrx.blocks) behind one autograd node each; parameters live in one flat buffer (asrx.params).
 
 Extra keyword-only knobs (not in the reference): precision ("bf16" training path | "fp32" parity path),
-attention ("fused" LDS-tiled kernel | "unfused" materialised scores + row softmax).
+attention ("fused" LDS-tiled kernel | "unfused" materialised scores + row softmax), ctc / ctc_blank (Transformer
+only: a CTC head on the encoder output, one extra state_dict key `ctc_head.weight`).
 """
 import math
 import weakref
@@ -208,7 +209,7 @@ class Transformer(nn.Module):
 
     def __init__(self, vocab_size, input_dim, embedding_dim, decoder_seq_len, encoder_seq_len, encoder_num_layers,
                  decoder_num_layers, num_heads, ff_dim, dropout=0.1, pad_token_id=4, eos_token_id=2, *,
-                 precision="bf16", attention="fused"):
+                 precision="bf16", attention="fused", ctc=False, ctc_blank=None):
         super().__init__()
         self.input_layer = FrontEnd()
         n_freq = subsampled(input_dim)
@@ -222,6 +223,15 @@ class Transformer(nn.Module):
                                eos_token_id=eos_token_id, dropout=dropout, pad_token_id=pad_token_id)
         self.precision = precision
         self.attention = attention
+        # ctc=True: a bias-free linear head on the encoder output (after Encoder._norm_out) for the hybrid
+        # CTC/attention objective (asrx.train.Trainer(ctc_weight=...)) and decoder-free best-path decoding.  Registered
+        # last, so every other parameter keeps its key, its initial values under a given seed and its place in the
+        # flat store; ctc=False builds exactly the reference's module tree.
+        self.ctc_blank = int(pad_token_id if ctc_blank is None else ctc_blank)
+        if ctc:
+            if not 0 <= self.ctc_blank < vocab_size:
+                raise ValueError(f"ctc_blank {self.ctc_blank} outside the vocabulary [0, {vocab_size})")
+            self.ctc_head = _Classifier(embedding_dim, vocab_size)
         _adopt(self)
 
     def forward(self, spectrum, text, mask):
@@ -236,3 +246,16 @@ class Transformer(nn.Module):
         """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1)."""
         from .functions import transformer_beam_search
         return transformer_beam_search(self, spectrum, text, **kw)
+
+    def ctc_logits(self, spectrum):
+        """Front end, encoder and the CTC head (ctc=True models), no grad: fp32 logits (B, T', V)."""
+        from .functions import transformer_ctc_logits
+        logits, B, T = transformer_ctc_logits(self, spectrum)
+        return logits.view(B, T, -1)[:, :, :self.ctc_head.V]
+
+    def ctc_greedy(self, spectrum, input_lengths=None):
+        """CTC best-path transcript without the decoder: per frame the arg-max of ctc_logits, repeats collapsed,
+        blanks removed, on the device.  input_lengths: (B,) valid encoder frames (None: all T').  Returns (tokens
+        (B, T') int64 left-packed and padded with the blank id, lengths (B,) int32), both on the device."""
+        from .functions import transformer_ctc_greedy
+        return transformer_ctc_greedy(self, spectrum, input_lengths)

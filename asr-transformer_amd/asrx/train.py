@@ -11,6 +11,9 @@ the GPU work): per-step values reach the replay through device memory (dropout s
 corrections), new batches are copied into the captured input buffers.  With a multi-GPU reducer the backward
 is captured in segments that end where gradient ranges become final; the RCCL all-reduce of each range is
 issued between segment replays, so it still overlaps the rest of the backward.
+
+`Trainer(..., ctc_weight=w)` on a `Transformer(..., ctc=True)` trains the hybrid objective (1 - w) * CE + w * CTC:
+the CTC launches (head GEMM, asrx_ctc_targets, asrx_ctc_loss, head data gradient) join the same captured chain.
 """
 import os
 
@@ -285,8 +288,23 @@ class Trainer:
     """Native data-parallel training step for an asrx.Transformer."""
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.98), eps=1e-9, weight_decay=0.0, decoupled=True,
-                 ignore_index=-100, group=None, bucket_mb=64, allreduce_fn=None, graph=None, wire=None, preds=False):
+                 ignore_index=-100, group=None, bucket_mb=64, allreduce_fn=None, graph=None, wire=None, preds=False,
+                 ctc_weight=0.0, bos_token_id=1):
         self.model = model
+        # ctc_weight w > 0: the hybrid objective (1 - w) * CE + w * CTC_mean, the CTC term on the model's ctc_head
+        # (Transformer(..., ctc=True)) over all T' encoder frames, its targets the step's text without BOS / EOS / PAD
+        # (asrx_ctc_targets), zero_infinity on.  w = 0 is the cross-entropy step, launch for launch; a ctc_head the
+        # model may carry is then frozen like the reference's unused parameters (no gradient, no AdamW, no decay).
+        self.ctc_weight = float(ctc_weight)
+        if not 0.0 <= self.ctc_weight < 1.0:
+            raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1)")
+        head = getattr(model, "ctc_head", None)
+        if self.ctc_weight > 0 and head is None:
+            raise ValueError("ctc_weight > 0 needs a model with a CTC head: Transformer(..., ctc=True)")
+        self._ctc_drop = [int(bos_token_id), int(model.decoder._eos_token_id)]
+        if model.decoder.pad_token_id is not None:
+            self._ctc_drop.append(int(model.decoder.pad_token_id))
+        idle_head = list(head.parameters()) if head is not None and self.ctc_weight == 0 else []
         self.store = get_store(model)
         self.m = torch.zeros_like(self.store.flat)
         self.v = torch.zeros_like(self.store.flat)
@@ -296,7 +314,7 @@ class Trainer:
         self.reducer = GradAllReduce(self.store.grad, group=group, bucket_mb=bucket_mb, allreduce_fn=allreduce_fn,
                                      wire=wire)
         self.store.refresh_shadow(force=True)
-        self._wonly = wgrad_only_params(model) if FRESH_GRADS else []
+        self._wonly = [p for p in wgrad_only_params(model) if not any(p is q for q in idle_head)] if FRESH_GRADS else []
         self.graph = GRAPH if graph is None else bool(graph)
         self._cap = None        # captured step of the current input shape: (segments, static inputs, loss, preds)
         self._caps = {}         # every captured step, keyed by input shapes (a smaller last batch keeps its own graph)
@@ -315,7 +333,7 @@ class Trainer:
         # parameters the reference never gives a gradient (input_encoding, model.py:173; Encoder._norm_in, model.py:12):
         # torch's AdamW skips a parameter whose grad is None, so every AdamW launch here leaves their ranges alone
         # (a zero-gradient step would still apply weight decay to them)
-        self._frozen = sorted((self.store.offset(p), p.numel()) for p in unused_params(model)
+        self._frozen = sorted((self.store.offset(p), p.numel()) for p in unused_params(model) + idle_head
                               if self.store.owns(p))
         if self._wonly:   # the spans of everything else, zeroed each step by one asrx_zero_spans launch
             n, spans, pos = self.store.grad.numel(), [], 0
@@ -354,19 +372,36 @@ class Trainer:
         model = self.model
         C = make_ctx(model, model.decoder.p)
         inp = text if input_text is None else input_text
+        lam = self.ctc_weight
         if (text.is_cuda and text.dtype == torch.int64 and inp.dtype == torch.int64 and mask.dtype == torch.float32
                 and text.stride(1) == 1 and inp.stride(1) == 1 and mask.stride(1) == 1):
             # the shifted inputs, targets and decoder mask in one native launch (no torch copies in the step)
             B, L = text.shape[0], text.shape[1] - 1
             dec_in, tgt, valid = K.step_tokens(text, inp, mask)
             spec = K.MaskSpec(1, True, valid, valid, valid.stride(0))
-            logits, S = model_forward(C, model, spectrum, dec_in.view(B, L), None, spec=spec)
+            logits, S = model_forward(C, model, spectrum, dec_in.view(B, L), None, spec=spec, ctc=lam > 0)
         else:
-            logits, S = model_forward(C, model, spectrum, inp[:, :-1], mask[:, :-1])
+            logits, S = model_forward(C, model, spectrum, inp[:, :-1], mask[:, :-1], ctc=lam > 0)
             tgt = text[:, 1:].reshape(-1).contiguous()
         V = model.decoder._classifier.V
-        loss, dl, am = K.cross_entropy(logits, V, tgt, ignore_index=self.ignore_index, want_argmax=self.want_preds)
+        loss, dl, am = K.cross_entropy(logits, V, tgt, ignore_index=self.ignore_index, grad_scale=1.0 - lam,
+                                       want_argmax=self.want_preds)
         self.last_preds = am
+        dctc = None
+        if lam > 0:
+            # (1 - w) * CE + w * CTC_mean: both gradients carry their weight, the sum is the CTC finishing launch's
+            dev = logits.device
+            tt = text.to(device=dev, dtype=torch.int64)
+            ctc_tgt, ctc_len = K.ctc_targets(tt if tt.stride(1) == 1 else tt.contiguous(),
+                                             mask.to(device=dev, dtype=torch.float32).contiguous(), self._ctc_drop,
+                                             model.ctc_blank)
+            cl = S["ctc_logits"]
+            Tp = cl.shape[0] // text.shape[0]
+            # (a row longer than the kernel's 255 labels has no alignment there: zero_infinity drops it)
+            loss, _, dctc = K.ctc_loss(cl, model.ctc_head.V, Tp, ctc_tgt, ctc_len,
+                                       max_target_len=min(ctc_tgt.shape[1], 255), blank=model.ctc_blank,
+                                       reduction="mean", zero_infinity=True, grad_scale=lam, grad_dtype=C.cd,
+                                       loss_add=loss, loss_add_scale=1.0 - lam, loss_scale=lam)
         if self._wonly and C.cd == torch.bfloat16 and all(p.grad is not None for p in self.store.params):
             K.zero_spans(self.store.grad, self._zero_spans)
             C.fresh = FreshGrads(self.store, self._wonly)
@@ -380,7 +415,7 @@ class Trainer:
                                  grad_scale=1.0 / self.reducer.world, decoupled=self.decoupled, hyp=self._hyp)
         if ready is None and not capture and self.reducer.active:
             ready = self.reducer.ready
-        model_backward(C, model, S, dl.to(C.cd) if dl.dtype != C.cd else dl, ready=ready)
+        model_backward(C, model, S, dl.to(C.cd) if dl.dtype != C.cd else dl, ready=ready, dctc_c=dctc)
         if C.fresh is not None:
             C.fresh.drain()
             C.fresh = None

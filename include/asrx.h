@@ -33,7 +33,7 @@ extern "C" {
 
 /* Library version / build identification (3: dq_acc holds one slab per key block, asrx_attn_dq_acc_elems;
  * asrx_adam_spans takes bounds that are not multiples of 4.  4: asrx_beam_step and asrx_gather_rows, the device half
- * of beam-search decoding). */
+ * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -402,6 +402,68 @@ int asrx_beam_step(const float* logits, int32_t B, int32_t W, int32_t V, int64_t
  * covers every decoder layer: outer = layers, rows = B*W, count = the filled prefix of a cache row. */
 int asrx_gather_rows(const void* src, void* dst, const int32_t* index, int32_t esize, int32_t outer, int32_t rows,
                      int64_t count, int64_t row_stride, int64_t outer_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * CTC (version >= 5): the second term of the hybrid objective (1 - w) * CE + w * CTC on a linear head over the encoder
+ * output.  The reference trains on cross-entropy alone (train.py:32); the user-side alternative these replace is
+ * log_softmax + F.ctc_loss + autograd.
+ * ------------------------------------------------------------------------------------------------- */
+#define ASRX_CTC_SUM 0    /* loss = sum_b nll_b,                              per-sample weight w_b = 1 */
+#define ASRX_CTC_MEAN 1   /* loss = mean_b(nll_b / max(target_len_b, 1)),     w_b = 1 / (B * max(target_len_b, 1)) */
+
+/* Number of fp32 workspace elements asrx_ctc_loss needs (row statistics, per-sample tables, and log2 alpha / beta of
+ * every (b, t) row: 128 * ceil((max_target_len + 1) / 64) values each); -1 on bad arguments (B, T <= 0,
+ * max_target_len outside [0, 255]).  Host-only arithmetic, no device access. */
+int64_t asrx_ctc_workspace_elems(int32_t B, int32_t T, int32_t max_target_len);
+
+/* CTC negative log-likelihood and its gradient with respect to the LOGITS (the log-softmax is fused; no
+ * log-probability tensor exists).  F.ctc_loss(F.log_softmax(logits, -1).transpose(0, 1), targets, input_lengths,
+ * target_lengths, blank, reduction, zero_infinity) and its backward.
+ *   logits          fp32, row b*T + t at logits + (b*T + t)*ld, ld >= V; only columns [0, V) are read
+ *   targets         int64 [B][tgt_stride]; sample b's labels are its first target_lengths[b] entries
+ *   input_lengths   device int32 [B], nullable (null = T for every sample); clamped to [0, T]
+ *   target_lengths  device int32 [B]
+ *   max_target_len  host-side bound of every target length, 0 <= max_target_len <= tgt_stride.  The lengths live on
+ *                   the device, so this is what the host checks: above 255 (511 extended states) the call returns
+ *                   ASRX_ERR_UNSUPPORTED before any device access.  It sizes the workspace and picks the kernel (each
+ *                   lane of a wave64 holds ceil((max_target_len + 1) / 64) <= 4 blank/label state pairs).
+ *   blank           0 <= blank < V, else ASRX_ERR_ARG (before any device access)
+ *   nll[B]          fp32 per sample; +inf where no alignment exists.  That is also the result of a sample the host
+ *                   cannot see to be malformed: a length outside [0, max_target_len], a label equal to blank or
+ *                   outside [0, V).  Such a label is never used as an index.
+ *   loss[1]         loss_add_scale * loss_add[0] + loss_scale * sum_b w_b nll_b  (loss_add nullable: the first term is
+ *                   dropped).  With zero_infinity, +inf terms count as 0.  Summed over b in a fixed order.
+ *                   The training step takes (1 - w) * CE + w * CTC from the finishing launch this way (a factor on
+ *                   both terms), with no torch arithmetic in the captured step.
+ *   dlogits         nullable; ASRX_BF16 or ASRX_F32 [B*T][ld]: grad_scale * w_b * (softmax - occupancy) in columns
+ *                   [0, V), zero in [V, ld) and in the rows t >= input_length_b.  grad_scale does not scale loss.  The
+ *                   rows of a sample without alignment are zero with zero_infinity and NaN without (as torch's).
+ *   ws              asrx_ctc_workspace_elems(B, T, max_target_len) floats, 16-B aligned; contents undefined after
+ * Deterministic: no floating-point atomics; the occupancy of a label that occurs several times in a target is summed
+ * in order of position, the batch in order of b — two calls on the same inputs give the same bits.  Four launches, no
+ * synchronisation, graph-capturable.  16-B accesses where ld % 4 == 0 and the bases are aligned, element accesses
+ * otherwise.  ld <= 8192, B <= 65535. */
+int asrx_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int64_t* targets,
+                  int64_t tgt_stride, const int32_t* input_lengths, const int32_t* target_lengths,
+                  int32_t max_target_len, int32_t blank, int32_t reduction, int32_t zero_infinity, float grad_scale,
+                  float* nll, float* loss, void* dlogits, int32_t dlogits_dtype, const float* loss_add,
+                  float loss_add_scale, float loss_scale, float* ws, int64_t ws_elems, void* stream);
+
+/* CTC targets of a teacher-forced batch: text int64 [B][n] (row stride ld_text; n = L + 1 columns of the step's token
+ * rows) and the float pad mask [B][n] (row stride ld_mask).  Per sample, in order, the tokens at positions with
+ * mask >= 1 that are none of drop[0 .. ndrop) (HOST array, ndrop <= 4: BOS, EOS, PAD / blank) go left-packed to
+ * targets[b][0 ..], the rest of the n columns are filled with `blank`; target_lengths[b] (int32) = the count.  One
+ * launch (cf. asrx_step_tokens). */
+int asrx_ctc_targets(const int64_t* text, int64_t ld_text, const float* mask, int64_t ld_mask, int32_t B, int32_t n,
+                     const int64_t* drop, int32_t ndrop, int64_t blank, int64_t* targets, int64_t ld_targets,
+                     int32_t* target_lengths, void* stream);
+
+/* CTC best-path decoding: per sample the first-index arg-max (asrx_greedy_argmax's tie rule) of every frame
+ * t < input_lengths[b] (nullable: T) over columns [0, V) of logits row b*T + t (fp32, row stride ld), repeated frames
+ * collapsed, blanks removed: tok[b][0 .. len[b]) (int64 [B][T], the rest = blank), len int32 [B].  One launch, no
+ * host round trip.  T <= 15360. */
+int asrx_ctc_greedy(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int32_t* input_lengths,
+                    int32_t blank, int64_t* tok, int32_t* len, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
