@@ -110,6 +110,7 @@ def kernel_name(d):
 PROBE = None
 
 # asrx_gemm_desc.kernel: forced kernel family (0 = auto).  ASRX_GEMM_KERNEL picks a process-wide default (A/B).
+# The values are asrx.h's ASRX_GEMM_AUTO, _P3, _REG, _RING, _RING128, _P4, _WS and _WS64.
 KERNEL_CODES = {"auto": 0, "p3": 1, "reg": 3, "ring": 4, "ring128": 5, "p4": 6, "ws": 8, "ws64": 10}
 GEMM_KERNEL = KERNEL_CODES.get(os.environ.get("ASRX_GEMM_KERNEL", "auto"), 0)
 
@@ -320,6 +321,7 @@ def xcd_plan(shapes, tile=256, nxcd=8, pack=None):
     return plan
 
 
+# grouped launch: kind -> (tile, common->tile code: asrx.h's ASRX_GROUP_TILE_P3, _P4, _WS and _REG)
 _TILE_CODE = {"p3": ((256, 128), 3), "p4": ((256, 256), 4), "ws": ((256, 128), 5), "reg": ((128, 128), 128)}
 
 

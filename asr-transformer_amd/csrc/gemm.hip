@@ -16,13 +16,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
+#include <type_traits>
 
 #include "gemm_common.h"
 
-
 namespace {
 using namespace asrxg;
-
 
 // ------------------------------------------------------------------------------------------------
 // bf16 kernel
@@ -239,12 +239,8 @@ __global__ __launch_bounds__(256) void gemm_bf16_grouped_dev_kernel(float alpha,
   if (tid >= ntiles) return;
   const int gi = __builtin_amdgcn_readfirstlane((int)tile_group[tid]);
   const GroupEnt e = ents[gi];
-  GemmArgs g = {};
-  g.M = e.m; g.N = e.n; g.K = e.k;
-  g.a = e.a; g.lda = e.lda; g.b = e.b; g.ldb = e.ldb; g.c = e.c; g.ldc = e.ldc; g.c_dtype = c_dtype;
-  g.batch_inner = 1; g.alpha = alpha; g.beta = beta; g.rowadd_mod = 1;
-  g.splitk = 1; g.k_per_split = ((e.k + BK - 1) / BK) * BK; g.cvec = cvec;
-  g.rowsum = e.rowsum;
+  GemmArgs g = group_args(e, alpha, beta, c_dtype, 0);
+  g.k_per_split = ((e.k + BK - 1) / BK) * BK; g.cvec = cvec;
   gemm_bf16_tile<128, 128, AT, BT, true>(g, tid - e.tile_start, 0, 0, lds);
 }
 
@@ -819,13 +815,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_p3g_kernel(float alpha, float b
   if (tid >= ntiles) return;
   const int gi = __builtin_amdgcn_readfirstlane((int)tile_group[tid]);
   const GroupEnt e = ents[gi];
-  GemmArgs g = {};
-  g.M = e.m; g.N = e.n; g.K = e.k;
-  g.a = e.a; g.lda = e.lda; g.b = e.b; g.ldb = e.ldb; g.c = e.c; g.ldc = e.ldc; g.c_dtype = c_dtype;
-  g.batch_inner = 1; g.alpha = alpha; g.beta = beta; g.rowadd_mod = 1;
-  g.splitk = 1; g.k_per_split = e.k; g.cvec = 1;
-  g.rowsum = e.rowsum;
-  g.dbg = dbg & 9;
+  const GemmArgs g = group_args(e, alpha, beta, c_dtype, dbg & 9);
   p3_body<true, true, EPI, 128>(g, TileSeq::single(tid - e.tile_start), 0, 0, lds);
 }
 template <int EPI>
@@ -839,52 +829,35 @@ __global__ __launch_bounds__(512) void gemm_bf16_p4g_kernel(float alpha, float b
   if (tid >= ntiles) return;
   const int gi = __builtin_amdgcn_readfirstlane((int)tile_group[tid]);
   const GroupEnt e = ents[gi];
-  GemmArgs g = {};
-  g.M = e.m; g.N = e.n; g.K = e.k;
-  g.a = e.a; g.lda = e.lda; g.b = e.b; g.ldb = e.ldb; g.c = e.c; g.ldc = e.ldc; g.c_dtype = c_dtype;
-  g.batch_inner = 1; g.alpha = alpha; g.beta = beta; g.rowadd_mod = 1;
-  g.splitk = 1; g.k_per_split = e.k; g.cvec = 1;
-  g.rowsum = e.rowsum;
-  g.dbg = dbg & 9;
+  const GemmArgs g = group_args(e, alpha, beta, c_dtype, dbg & 9);
   p4_body<true, true, EPI, 256>(g, TileSeq::single(tid - e.tile_start), 0, 0, lds);
 }
 
 int launch_p3_grouped(const asrx_gemm_desc* common, const GroupEnt* ents, const uint16_t* tile_group,
                       const uint16_t* block_tile, int ntiles, int blocks, bool p4, hipStream_t st) {
-  if (common->c_dtype != ASRX_F32 || common->alpha != 1.f) return -1;
-  if (common->beta != 1.f && common->beta != 0.f) return -1;
-#define ASRX_G(KER, E) hipLaunchKernelGGL((KER<E>), dim3(blocks), dim3(P_THREADS), 0, st, common->alpha, common->beta, \
-                                          common->c_dtype, ents, tile_group, block_tile, ntiles, gemm_dbg())
-  if (p4) {
-    if (common->beta == 1.f) ASRX_G(gemm_bf16_p4g_kernel, E_BETA | E_F32);
-    else ASRX_G(gemm_bf16_p4g_kernel, E_F32);
-  } else {
-    if (common->beta == 1.f) ASRX_G(gemm_bf16_p3g_kernel, E_BETA | E_F32);
-    else ASRX_G(gemm_bf16_p3g_kernel, E_F32);
-  }
-#undef ASRX_G
+  if (common->c_dtype != ASRX_F32 || common->alpha != 1.f || (common->beta != 1.f && common->beta != 0.f)) return -1;
+  const bool acc = common->beta == 1.f;
+  auto* kernel = p4 ? (acc ? gemm_bf16_p4g_kernel<E_BETA | E_F32> : gemm_bf16_p4g_kernel<E_F32>)
+                    : (acc ? gemm_bf16_p3g_kernel<E_BETA | E_F32> : gemm_bf16_p3g_kernel<E_F32>);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(P_THREADS), 0, st, common->alpha, common->beta, common->c_dtype, ents,
+                     tile_group, block_tile, ntiles, gemm_dbg());
   return 0;
 }
 
 template <bool AT, bool BT, int EPI, bool P4>
 void launch_p3(const GemmArgs& g, int ntiles, int splitk, int batch, hipStream_t st) {
-  const int per = splitk * batch;
-  const int gx = std::max(1, std::min(ntiles, std::max(1, 256 / per)));
+  const dim3 grid(std::max(1, std::min(ntiles, std::max(1, 256 / (splitk * batch)))), splitk, batch);
   // XCD-contiguous tile order: measured 1-7% faster on the c3 shapes than round-robin (round 3 A/B)
   constexpr int xcd = 1;
-  if constexpr (P4)
-    hipLaunchKernelGGL((gemm_bf16_p4_kernel<AT, BT, EPI>), dim3(gx, splitk, batch), dim3(P_THREADS), 0, st, g, ntiles,
-                       xcd);
-  else
-    hipLaunchKernelGGL((gemm_bf16_p3_kernel<AT, BT, EPI>), dim3(gx, splitk, batch), dim3(P_THREADS), 0, st, g,
-                       ntiles, xcd);
+  if constexpr (P4) hipLaunchKernelGGL((gemm_bf16_p4_kernel<AT, BT, EPI>), grid, dim3(P_THREADS), 0, st, g, ntiles, xcd);
+  else hipLaunchKernelGGL((gemm_bf16_p3_kernel<AT, BT, EPI>), grid, dim3(P_THREADS), 0, st, g, ntiles, xcd);
 }
 
 // p4 (256x256 tiles) instantiations: the epilogues of the wide projection GEMMs it is planned for (the
 // residual epilogues of the N = 512 GEMMs, whose prefetched operands would not fit the registers beside the
-// 128x64 accumulator tile, stay on p3)
-#define ASRX_EPI4_NT(X) X(E_BIAS) X(E_BIAS | E_RELU) X(E_BIAS | E_RELU | E_DROP) X(E_F32) X(0) \
-  X(E_BIAS | E_RELU | E_MASKOUT) X(E_BIAS | E_RELU | E_DROP | E_MASKOUT)
+// 128x64 accumulator tile, stay on p3).  Bias + ReLU (+ mask bits) without dropout is not in the list: the plan runs
+// it as the dropout instantiation with threshold 0 (plan_bf16)
+#define ASRX_EPI4_NT(X) X(E_BIAS) X(E_BIAS | E_RELU | E_DROP) X(E_F32) X(0) X(E_BIAS | E_RELU | E_DROP | E_MASKOUT)
 #define ASRX_EPI4_NN(X) X(0) X(E_F32) X(E_GBITS) X(E_GBITS | E_ALPHA)
 #define ASRX_EPI4_TT(X) X(E_BETA | E_F32) X(E_F32)
 
@@ -899,31 +872,19 @@ bool p4_instantiated(bool at, bool bt, int epi) {
 
 template <bool AT, bool BT, bool P4 = false>
 void dispatch_p3(const GemmArgs& g, int epi, int ntiles, int splitk, int batch, hipStream_t st) {
-#define ASRX_CASE(E) \
-  case (E): launch_p3<AT, BT, (E), P4>(g, ntiles, splitk, batch, st); return;
-  if constexpr (P4) {
-    if constexpr (!AT && !BT) {
-      switch (epi) { ASRX_EPI4_NT(ASRX_CASE) default: break; }
-    } else if constexpr (!AT && BT) {
-      switch (epi) { ASRX_EPI4_NN(ASRX_CASE) default: break; }
-    } else if constexpr (AT && BT) {
-      switch (epi) { ASRX_EPI4_TT(ASRX_CASE) default: break; }
-    }
-    return;   // (the planner only picks p4 for an instantiated epilogue)
-  } else if constexpr (!AT && !BT) {
-    switch (epi) { ASRX_EPI_NT(ASRX_CASE) default: break; }
-  } else if constexpr (!AT && BT) {
-    switch (epi) { ASRX_EPI_NN(ASRX_CASE) default: break; }
-  } else if constexpr (AT && BT) {
-    switch (epi) { ASRX_EPI_TT(ASRX_CASE) default: break; }
-  }
+#define ASRX_CASE(E) case (E): launch_p3<AT, BT, (E), P4>(g, ntiles, splitk, batch, st); return;
+#define ASRX_SWITCH(LIST3, LIST4)                                   \
+  if constexpr (P4) { switch (epi) { LIST4(ASRX_CASE) default: break; } } \
+  else { switch (epi) { LIST3(ASRX_CASE) default: break; } }
+  if constexpr (!AT && !BT) { ASRX_SWITCH(ASRX_EPI_NT, ASRX_EPI4_NT) }
+  else if constexpr (!AT && BT) { ASRX_SWITCH(ASRX_EPI_NN, ASRX_EPI4_NN) }
+  else if constexpr (AT && BT) { ASRX_SWITCH(ASRX_EPI_TT, ASRX_EPI4_TT) }
+#undef ASRX_SWITCH
 #undef ASRX_CASE
+  // p3 runs everything else on its generic epilogue (the planner only picks p4 for an instantiated one)
   if constexpr (!P4) launch_p3<AT, BT, E_GENERIC, false>(g, ntiles, splitk, batch, st);
 }
 
-// ------------------------------------------------------------------------------------------------
-// fp32 kernel (exact fp32 MFMA; parity path)
-// ------------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------------
 // bf16 "ring" kernel for small output grids (e.g. the decoder's M = B*L = 4096 projections): BMxBN tiles
 // (64x64 or 128x64), 4 waves (2x2), one tile per workgroup, a 4-stage LDS-DMA ring so three K-steps are in
@@ -1073,22 +1034,25 @@ __global__ __launch_bounds__(256) void gemm_bf16_ring_kernel(GemmArgs g, int nti
   }
 }
 
-template <int BM, int BN, bool AT, bool BT>
-void dispatch_ring(const GemmArgs& g, int epi, int splitk, int batch, hipStream_t st) {
-  const int ntiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+// (k-contiguous A only: the planner picks no ring for A^T)
+template <int BM, int BN, bool BT>
+void dispatch_ring(const GemmArgs& g, int epi, int ntiles, int batch, hipStream_t st) {
   constexpr int xcd = 1;   // XCD-contiguous tile order (as p3)
-  dim3 grid(xcd ? 8 * ((ntiles + 7) / 8) : ntiles, splitk, batch);
+  dim3 grid(xcd ? 8 * ((ntiles + 7) / 8) : ntiles, g.splitk, batch);
 #define ASRX_CASE(E) \
-  case (E): hipLaunchKernelGGL((gemm_bf16_ring_kernel<BM, BN, AT, BT, (E)>), grid, dim3(R_THREADS), 0, st, g, ntiles, xcd); return;
-  if constexpr (!AT && !BT) {
+  case (E): hipLaunchKernelGGL((gemm_bf16_ring_kernel<BM, BN, false, BT, (E)>), grid, dim3(R_THREADS), 0, st, g, ntiles, xcd); return;
+  if constexpr (!BT) {
     switch (epi) { ASRX_EPI_NT(ASRX_CASE) default: break; }
-  } else if constexpr (!AT && BT) {
+  } else {
     switch (epi) { ASRX_EPI_NN(ASRX_CASE) default: break; }
   }
 #undef ASRX_CASE
-  hipLaunchKernelGGL((gemm_bf16_ring_kernel<BM, BN, AT, BT, E_GENERIC>), grid, dim3(R_THREADS), 0, st, g, ntiles, xcd);
+  hipLaunchKernelGGL((gemm_bf16_ring_kernel<BM, BN, false, BT, E_GENERIC>), grid, dim3(R_THREADS), 0, st, g, ntiles, xcd);
 }
 
+// ------------------------------------------------------------------------------------------------
+// fp32 kernel (exact fp32 MFMA; parity path)
+// ------------------------------------------------------------------------------------------------
 constexpr int FBM = 64, FBN = 64, FBK = 16, FSTRIDE = 64 + 16;
 
 template <bool KSTRIDED>
@@ -1458,35 +1422,37 @@ __global__ __launch_bounds__(256) void rowsum_finish_kernel(const float* ws, int
   if (sg == 0 && m < M) out[m] += red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-template <int BM, int BN, bool AT, bool BT, bool VEC>
-void launch_bf16(const GemmArgs& g, int ntiles, int batch, hipStream_t st) {
-  dim3 grid(ntiles, g.splitk, batch);
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, AT, BT, VEC>), grid, dim3(256), 0, st, g);
-}
-
-template <int BM, int BN>
-void dispatch_bf16(const GemmArgs& g, bool at, bool bt, bool vec, int batch, hipStream_t st) {
-  const int ntiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-#define ASRX_L(AT_, BT_)                                                   \
-  if (vec) launch_bf16<BM, BN, AT_, BT_, true>(g, ntiles, batch, st);      \
-  else launch_bf16<BM, BN, AT_, BT_, false>(g, ntiles, batch, st);
-  if (!at && !bt) { ASRX_L(false, false) }
-  else if (!at && bt) { ASRX_L(false, true) }
-  else if (at && !bt) { ASRX_L(true, false) }
-  else { ASRX_L(true, true) }
-#undef ASRX_L
-}
-
-
 // ------------------------------------------------------------------------------------------------
-// Kernel selection (shared by asrx_gemm and asrx_gemm_kernel_name so profiling can name the launch).
+// Host side: layout dispatch, the plan (kernel selection), its name, its launch.
+// Run-time (a_trans, b_trans) as compile-time constants: calls f(AT, BT) with std::bool_constant arguments.
+template <class F>
+void with_layout(bool at, bool bt, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  at ? (bt ? f(T{}, T{}) : f(T{}, N{})) : (bt ? f(N{}, T{}) : f(N{}, N{}));
+}
+// ... and the operand alignment: f(AT, BT, VEC)
+template <class F>
+void with_layout(bool at, bool bt, bool vec, F&& f) {
+  with_layout(at, bt, [&](auto AT, auto BT) { vec ? f(AT, BT, std::true_type{}) : f(AT, BT, std::false_type{}); });
+}
+
+// The bf16 kernel families: register-staged 128x128 / 64x64 tiles, the 256x128 / 256x256 LDS-DMA rings, the 64x64 /
+// 128x64 4-stage LDS-DMA rings (small grids), the many-split tall-K kernel (conv2 dW), ws on 256x128 / 64x128 tiles
+enum class Family { Reg128, Reg64, P3, P4, Ring64, Ring128, TallK, Ws256, Ws64 };
+enum class Reduce { None, SplitK, TallK };   // the split-K finish after the GEMM kernel
+
+// Everything asrx_gemm launches for one bf16 descriptor.  asrx_gemm_kernel_name formats the same plan (plan_name),
+// so profiling names the kernel that runs.
 struct GemmPlan {
-  int use;     // 1 = p3 (256x128 LDS-DMA ring), 2 = p4 (256x256), 3 = register path 128, 4 = register path 64,
-               // 5 = ring 64x64, 6 = ring 128x64 (4-stage LDS-DMA, small grids), 9 = tall-K (conv2 dW),
-               // 11 = ws (warp-specialised 256x128, one-round N = 512 outputs), 13 = ws on 64x128 tiles
-  bool vec;    // 16-byte aligned operands
-  int epi;     // instantiated epilogue flags (E_GENERIC when the fast-path set has no match)
-  int ntiles;  // output tiles of the chosen kernel
+  Family family;
+  bool at, bt;         // operand layouts
+  bool vec, cvec;      // 16-byte aligned operands; aligned C quads (c_quads_aligned)
+  int epi;             // epilogue flags as launched (E_GENERIC when the fast-path set has no match)
+  bool drop_keeps_all; // epi's E_DROP is p4's stand-in for "no dropout": the launch sets threshold 0, scale 1
+  int ntiles;          // output tiles of the chosen kernel
+  bool bias_chunks;    // p3 / p4 bias epilogue on an output wider than its LDS bias stage: runs as column chunks
+  Reduce reduce;
 };
 
 bool epi_instantiated(bool at, bool bt, int epi) {
@@ -1498,6 +1464,26 @@ bool epi_instantiated(bool at, bool bt, int epi) {
   return false;
 }
 
+// asrx_gemm_desc.kernel -> the family it forces (`reg`: the register family of the descriptor's tile); none = auto:
+// ASRX_GEMM_AUTO, the retired codes and unknown ones
+std::optional<Family> forced_family(int code, Family reg) {
+  switch (code) {
+    case ASRX_GEMM_P3: return Family::P3;
+    case ASRX_GEMM_REG: return reg;
+    case ASRX_GEMM_RING: return Family::Ring64;
+    case ASRX_GEMM_RING128: return Family::Ring128;
+    case ASRX_GEMM_P4: return Family::P4;
+    case ASRX_GEMM_WS: return Family::Ws256;
+    case ASRX_GEMM_WS64: return Family::Ws64;
+    default: return std::nullopt;
+  }
+}
+
+bool c_quads_aligned(const asrx_gemm_desc* d) {
+  const int esz = d->c_dtype == ASRX_F32 ? 16 : 8;
+  return (d->ldc % 4 == 0) && ((uintptr_t)d->c % esz == 0) && (d->sc_outer % 4 == 0) && (d->sc_inner % 4 == 0);
+}
+
 // Planner constants (round 5: their A/B environment switches were removed; measurements in DESIGN §4):
 // * ws for the N = 512 encoder GEMMs (faster than p3 at every c3 shape);
 // * ws with 64 x 128 tiles (64 x 4 = 256 tiles = one per CU) for the decoder's 2048 <= M < 8192, N = 512 GEMMs
@@ -1507,66 +1493,55 @@ bool epi_instantiated(bool at, bool bt, int epi) {
 // * ws from the shortest reduction up (every K from 512 up measured faster than p3 at c3);
 // * p4 only from 400 256x256 tiles up (wave quantisation: the c3 Q/K/V projection has 378 such tiles = 1.48 rounds
 //   over 256 CUs, 756 p3 tiles = 2.95 rounds).
-constexpr bool ws_auto() { return true; }
-constexpr bool ws64_auto() { return true; }
-constexpr bool ws_qkv_auto() { return true; }
 constexpr int ws_min_k() { return 64; }
 constexpr int p4_min_tiles() { return 400; }
 
 GemmPlan plan_bf16(const asrx_gemm_desc* d, int batch, int splitk) {
-  GemmPlan pl;
+  GemmPlan pl = {};
+  pl.at = d->a_trans != 0, pl.bt = d->b_trans != 0;
   pl.vec = (d->lda % 8 == 0) && (d->ldb % 8 == 0) && ((uintptr_t)d->a % 16 == 0) && ((uintptr_t)d->b % 16 == 0) &&
            (d->sa_outer % 8 == 0) && (d->sa_inner % 8 == 0) && (d->sb_outer % 8 == 0) && (d->sb_inner % 8 == 0);
+  pl.cvec = c_quads_aligned(d);
   int tile = d->tile;
   if (tile != 64 && tile != 128) {
     const long t128 = (long)((d->m + 127) / 128) * ((d->n + 127) / 128) * batch * splitk;
     tile = t128 >= 400 ? 128 : 64;
   }
-  const int kvar = d->kernel == 1 ? 1 : d->kernel == 3 ? 3 : d->kernel == 4 ? 4 : d->kernel == 5 ? 5 :
-                   d->kernel == 6 ? 6 : d->kernel == 8 ? 8 : d->kernel == 10 ? 10 : 0;
-  const bool dma_ok = pl.vec && d->k % BK == 0 && (!d->a_trans || d->m % 8 == 0) && (!d->b_trans || d->n % 8 == 0) &&
+  const Family reg = tile == 128 ? Family::Reg128 : Family::Reg64;
+  const std::optional<Family> forced = forced_family(d->kernel, reg);
+  const bool dma_ok = pl.vec && d->k % BK == 0 && (!pl.at || d->m % 8 == 0) && (!pl.bt || d->n % 8 == 0) &&
                       d->m >= 8 && d->n >= 8;
   const int nt_p3 = ((d->m + P_BM - 1) / P_BM) * ((d->n + P_BN - 1) / P_BN);
   const int nt_p4 = ((d->m + P_BM - 1) / P_BM) * ((d->n + 255) / 256);
-  pl.use = tile == 128 ? 3 : 4;
   const int nt_r128 = ((d->m + 127) / 128) * ((d->n + 63) / 64);
+  pl.family = reg;
   if (dma_ok) {
-    if (kvar == 1) pl.use = 1;
-    else if (kvar == 6) pl.use = 2;
-    else if (kvar == 4 && !d->a_trans) pl.use = 5;
-    else if (kvar == 5 && !d->a_trans) pl.use = 6;
+    if (forced == Family::P3 || forced == Family::P4) pl.family = *forced;
+    else if ((forced == Family::Ring64 || forced == Family::Ring128) && !pl.at) pl.family = *forced;
     // auto (measured on the c3 shapes, tools/gemm_bench.py): the p3 ring wins every projection with K <= 4096
     // whose grid fills the chip; smaller grids (the decoder's 4096-row GEMMs) take the 4-stage ring kernel; the
     // register path wins the weight-gradient (A^T, reduction over B*T rows) and very long-K GEMMs.
     // (with the inline-asm LDS-DMA, p3 also wins the long-K cross-attention K/V data gradient, K = 12 288)
-    // (a forced ws-family code, 8 or 10, on a GEMM that family cannot take plans as auto)
-    else if ((kvar == 0 || kvar >= 8) && !d->a_trans) {
+    // (a forced ws family on a GEMM that family cannot take plans as auto)
+    else if ((!forced || forced == Family::Ws256 || forced == Family::Ws64) && !pl.at) {
       // wide outputs whose 256x256 tiles still fill the chip (>= 1.25 tiles per CU; the c3 FFN1 forward, the gated
       // FFN2 data gradient, the Q/K/V and cross K/V projections) take p4: half the operand ingest per FLOP
       // (tools/blas_ref.py: FFN1 forward 47 -> 39 us, FFN2 data gradient 52 -> 41 us); the N = 512 outputs (126
       // such tiles) stay on p3
-      if (nt_p4 * splitk * batch >= p4_min_tiles() && splitk == 1 && batch == 1) pl.use = 2;
-      else if (nt_p3 * splitk * batch >= 192) pl.use = 1;
+      if (nt_p4 * splitk * batch >= p4_min_tiles() && splitk == 1 && batch == 1) pl.family = Family::P4;
+      else if (nt_p3 * splitk * batch >= 192) pl.family = Family::P3;
       // (64x64 tiles also win the long-K decoder GEMMs, K >= 1536: 4 x more workgroups to cover the latency)
-      else pl.use = (nt_r128 * splitk * batch >= 192 && d->k < 1536) ? 6 : 5;
+      else pl.family = (nt_r128 * splitk * batch >= 192 && d->k < 1536) ? Family::Ring128 : Family::Ring64;
     }
   }
   // tall-K weight gradient (conv2 dW: 64 x 576 outputs, ~300k-row reduction): many-split LDS-DMA kernel
   // (ragged K is fine: rows past a split's end read as zeros)
-  if (pl.vec && kvar == 0 && d->a_trans && d->b_trans && d->m == 64 && d->n % 64 == 0 && d->n <= TK_MAXN &&
-      splitk >= 64 && batch == 1 && d->lda % 8 == 0 && d->ldb % 8 == 0)
-    pl.use = 9;
-  if (pl.use == 9) pl.ntiles = splitk;
-  else if (pl.use == 1) pl.ntiles = nt_p3;
-  else if (pl.use == 2) pl.ntiles = nt_p4;
-  else if (pl.use == 5) pl.ntiles = ((d->m + 63) / 64) * ((d->n + 63) / 64);
-  else if (pl.use == 6) pl.ntiles = nt_r128;
-  else pl.ntiles = ((d->m + tile - 1) / tile) * ((d->n + tile - 1) / tile);
+  if (pl.vec && !forced && pl.at && pl.bt && d->m == 64 && d->n % 64 == 0 && d->n <= TK_MAXN && splitk >= 64 &&
+      batch == 1 && d->lda % 8 == 0 && d->ldb % 8 == 0)
+    pl.family = Family::TallK;
   // compile-time epilogue selection (fast-path preconditions, else generic)
   int epi = E_GENERIC;
-  const int esz = d->c_dtype == ASRX_F32 ? 16 : 8;
-  const bool cvec = (d->ldc % 4 == 0) && ((uintptr_t)d->c % esz == 0) && (d->sc_outer % 4 == 0) && (d->sc_inner % 4 == 0);
-  const bool fast = batch == 1 && splitk == 1 && d->n % 4 == 0 && cvec &&
+  const bool fast = batch == 1 && splitk == 1 && d->n % 4 == 0 && pl.cvec &&
                     (!d->bias || (uintptr_t)d->bias % 16 == 0) &&
                     (!d->rowadd || (d->ld_rowadd % 4 == 0 && (uintptr_t)d->rowadd % 16 == 0)) &&
                     (!d->gate || (d->gate_dtype == ASRX_BF16 && d->ld_gate % 4 == 0 && (uintptr_t)d->gate % 8 == 0) ||
@@ -1579,35 +1554,198 @@ GemmPlan plan_bf16(const asrx_gemm_desc* d, int batch, int splitk) {
           (d->resid ? E_RESID : 0) | (d->beta == 1.f ? E_BETA : 0) |
           (d->c_dtype == ASRX_F32 ? E_F32 : 0) | (d->alpha != 1.f ? E_ALPHA : 0) | (d->rowadd ? E_ROWADD : 0);
   }
-  pl.epi = ((pl.use == 1 || pl.use == 2 || pl.use == 5 || pl.use == 6) && epi_instantiated(d->a_trans, d->b_trans, epi))
-               ? epi : E_GENERIC;
-  if (pl.use == 2 && (splitk != 1 || batch != 1 || !p4_instantiated(d->a_trans, d->b_trans, pl.epi))) {
-    pl.use = 1;   // p4 takes single, unsplit GEMMs with its instantiated epilogues; the rest stays on p3
-    pl.ntiles = nt_p3;
-  }
-  // ws (use 11): the warp-specialised 256x128 tiles for the N = 512 outputs that make one round of tiles on the
-  // chip (c3, every encoder GEMM with a 512-wide output: _lin_in + PE, the out-projection with dropout + residual,
-  // the FFN2 forward with bias + fp32 residual, the Q/K/V, FFN1 and out-projection data gradients; tools/blas_ref.py:
-  // 13.8-36.2 us against p3's 16.6-51.1 and hipBLASLt's 18.7-35.4 on the plain ones); kernel code 8 forces it for
+  const bool ring_family = pl.family == Family::P3 || pl.family == Family::P4 || pl.family == Family::Ring64 ||
+                           pl.family == Family::Ring128;
+  pl.epi = ring_family && epi_instantiated(pl.at, pl.bt, epi) ? epi : E_GENERIC;
+  // ws: the warp-specialised 256x128 tiles for the N = 512 outputs that make one round of tiles on the chip (c3,
+  // every encoder GEMM with a 512-wide output: _lin_in + PE, the out-projection with dropout + residual, the FFN2
+  // forward with bias + fp32 residual, the Q/K/V, FFN1 and out-projection data gradients; tools/blas_ref.py:
+  // 13.8-36.2 us against p3's 16.6-51.1 and hipBLASLt's 18.7-35.4 on the plain ones); ASRX_GEMM_WS forces it for
   // any GEMM it can take.
-  const bool ws_ok = dma_ok && !d->a_trans && batch == 1 && splitk == 1 && d->n % WS_BN == 0 && d->k >= BK &&
+  const bool ws_ok = dma_ok && !pl.at && batch == 1 && splitk == 1 && d->n % WS_BN == 0 && d->k >= BK &&
                      !d->rowsum_a && !d->mask_out && !d->sc_outer && !d->sc_inner && epi != E_GENERIC &&
-                     ws_instantiated(d->b_trans, epi);
-  const bool ws_qkv = ws_qkv_auto() && d->n == 1536 && d->m >= 4096 && !d->b_trans && (epi & E_BIAS) != 0;
-  if (ws_ok && (kvar == 8 || (kvar == 0 && ws_auto() && ((d->n == 512 && d->m >= 8192 && d->k >= ws_min_k()) ||
-                                                          ws_qkv)))) {
-    pl.use = 11;
+                     ws_instantiated(pl.bt, epi);
+  const bool ws_qkv = d->n == 1536 && d->m >= 4096 && !pl.bt && (epi & E_BIAS) != 0;
+  if (ws_ok && (forced == Family::Ws256 ||
+                (!forced && ((d->n == 512 && d->m >= 8192 && d->k >= ws_min_k()) || ws_qkv)))) {
+    pl.family = Family::Ws256;
     pl.epi = epi;
-    pl.ntiles = ((d->m + WS_BM - 1) / WS_BM) * (d->n / WS_BN);
-  } else if (ws_ok && (kvar == 10 || (kvar == 0 && ws64_auto() && d->n == 512 && d->m >= 2048 && d->m < 8192 &&
-                                      d->k >= ws_min_k()))) {
-    // ws on 64 x 128 tiles (use 13): the decoder's 4096-row GEMMs with a 512-wide output, where 256 x 128 tiles
-    // would make 64 workgroups; kernel code 10 forces it
-    pl.use = 13;
+  } else if (ws_ok && (forced == Family::Ws64 ||
+                       (!forced && d->n == 512 && d->m >= 2048 && d->m < 8192 && d->k >= ws_min_k()))) {
+    // ws on 64 x 128 tiles: the decoder's 4096-row GEMMs with a 512-wide output, where 256 x 128 tiles would make
+    // 64 workgroups; ASRX_GEMM_WS64 forces it
+    pl.family = Family::Ws64;
     pl.epi = epi;
-    pl.ntiles = ((d->m + 63) / 64) * (d->n / WS_BN);
+  } else if (pl.family == Family::P4) {
+    // p4's bias + ReLU (+ mask bits) instantiations without dropout spilled registers into the K-loop (the
+    // allocator's margin at ~240 VGPRs; the dropout ones do not) and are gone: they run as the dropout epilogue with
+    // threshold 0 and scale 1 — every element kept, v * 1.0 = v exactly (eval FFN1 forward 69.9 -> ~57 us alone,
+    // round 5)
+    const bool keeps_all = pl.epi == (E_BIAS | E_RELU) || pl.epi == (E_BIAS | E_RELU | E_MASKOUT);
+    const int epi4 = keeps_all ? pl.epi | E_DROP : pl.epi;
+    if (splitk == 1 && batch == 1 && p4_instantiated(pl.at, pl.bt, epi4)) {
+      pl.epi = epi4;
+      pl.drop_keeps_all = keeps_all;
+    } else {
+      pl.family = Family::P3;   // p4 takes single, unsplit GEMMs with its instantiated epilogues; the rest stays on p3
+    }
   }
+  switch (pl.family) {
+    case Family::Reg128: case Family::Reg64: pl.ntiles = ((d->m + tile - 1) / tile) * ((d->n + tile - 1) / tile); break;
+    case Family::P3: pl.ntiles = nt_p3; break;
+    case Family::P4: pl.ntiles = nt_p4; break;
+    case Family::Ring64: pl.ntiles = ((d->m + 63) / 64) * ((d->n + 63) / 64); break;
+    case Family::Ring128: pl.ntiles = nt_r128; break;
+    case Family::TallK: pl.ntiles = splitk; break;
+    case Family::Ws256: pl.ntiles = ((d->m + WS_BM - 1) / WS_BM) * (d->n / WS_BN); break;
+    case Family::Ws64: pl.ntiles = ((d->m + 63) / 64) * (d->n / WS_BN); break;
+  }
+  // the p3 / p4 bias epilogue stages the whole bias vector in LDS (16 KiB): wider outputs run as column chunks
+  pl.bias_chunks = (pl.family == Family::P3 || pl.family == Family::P4) && pl.epi != E_GENERIC && (pl.epi & E_BIAS) &&
+                   d->n > P_BIAS_BYTES / 4;
+  pl.reduce = splitk <= 1 ? Reduce::None : pl.family == Family::TallK ? Reduce::TallK : Reduce::SplitK;
   return pl;
+}
+
+// The kernel instantiation launch_plan enqueues for `pl`, as rocprofv3 lists it.
+void plan_name(const GemmPlan& pl, char* buf, int len) {
+  const char* tf[2] = {"false", "true"};
+  const char *at = tf[pl.at], *bt = tf[pl.bt];
+  switch (pl.family) {
+    case Family::Reg128: snprintf(buf, len, "gemm_bf16_kernel<128, 128, %s, %s, %s>", at, bt, tf[pl.vec]); break;
+    case Family::Reg64: snprintf(buf, len, "gemm_bf16_kernel<64, 64, %s, %s, %s>", at, bt, tf[pl.vec]); break;
+    case Family::P3: snprintf(buf, len, "gemm_bf16_p3_kernel<%s, %s, %d>", at, bt, pl.epi); break;
+    case Family::P4: snprintf(buf, len, "gemm_bf16_p4_kernel<%s, %s, %d>", at, bt, pl.epi); break;
+    case Family::Ring64: snprintf(buf, len, "gemm_bf16_ring_kernel<64, 64, %s, %s, %d>", at, bt, pl.epi); break;
+    case Family::Ring128: snprintf(buf, len, "gemm_bf16_ring_kernel<128, 64, %s, %s, %d>", at, bt, pl.epi); break;
+    case Family::TallK: snprintf(buf, len, "gemm_bf16_tallk_kernel"); break;
+    case Family::Ws256: snprintf(buf, len, "gemm_bf16_ws_kernel<%s, %d, 256>", bt, pl.epi); break;
+    case Family::Ws64: snprintf(buf, len, "gemm_bf16_ws_kernel<%s, %d, 64>", bt, pl.epi); break;
+  }
+}
+
+// Enqueue the bf16 plan `pl` on the arguments `g` (asrx_gemm after fill_args).
+int launch_plan(const asrx_gemm_desc* d, GemmArgs g, const GemmPlan& pl, int batch, hipStream_t st) {
+  if (pl.drop_keeps_all) g.drop_thr = 0u, g.drop_scale = 1.f;
+  // the bit-mask output is written only by the paired bf16 store path of the fast epilogues
+  if (d->mask_out && (!(pl.epi != E_GENERIC && (pl.epi & E_MASKOUT)) || !d->relu || d->c_dtype != ASRX_BF16 ||
+                      d->n % 32 != 0 || d->ldc % 8 != 0 || (uintptr_t)d->c % 16 != 0 ||
+                      (uintptr_t)d->mask_out % 4 != 0 || d->ld_mask < d->n / 32))
+    return ASRX_ERR_UNSUPPORTED;
+  switch (pl.family) {
+    case Family::Reg128:
+    case Family::Reg64:
+      with_layout(pl.at, pl.bt, pl.vec, [&](auto AT, auto BT, auto VEC) {
+        const dim3 grid(pl.ntiles, g.splitk, batch);
+        if (pl.family == Family::Reg128) hipLaunchKernelGGL((gemm_bf16_kernel<128, 128, AT, BT, VEC>), grid, dim3(256), 0, st, g);
+        else hipLaunchKernelGGL((gemm_bf16_kernel<64, 64, AT, BT, VEC>), grid, dim3(256), 0, st, g);
+      });
+      break;
+    case Family::P3:
+    case Family::P4: {
+      auto run = [&](const GemmArgs& ga, int ntiles) {
+        with_layout(pl.at, pl.bt, [&](auto AT, auto BT) {
+          if (pl.family == Family::P4) dispatch_p3<AT, BT, true>(ga, pl.epi, ntiles, g.splitk, batch, st);
+          else dispatch_p3<AT, BT>(ga, pl.epi, ntiles, g.splitk, batch, st);
+        });
+      };
+      if (!pl.bias_chunks) {
+        run(g, pl.ntiles);
+        break;
+      }
+      // (fast-path epilogues without dropout only: their element math does not depend on N — the threshold-0 dropout
+      // above keeps every element whatever its hash index)
+      if (((pl.epi & E_DROP) && !pl.drop_keeps_all) || pl.at || pl.bt || batch != 1 || g.splitk != 1)
+        return ASRX_ERR_UNSUPPORTED;
+      for (int c0 = 0; c0 < d->n; c0 += P_BIAS_BYTES / 4) {
+        GemmArgs gc = g;
+        gc.N = std::min(P_BIAS_BYTES / 4, d->n - c0);
+        gc.b = (const bf16_t*)d->b + (int64_t)c0 * d->ldb;
+        gc.bias = d->bias + c0;
+        gc.c = (char*)d->c + (int64_t)c0 * (d->c_dtype == ASRX_F32 ? 4 : 2);
+        if (gc.rowadd) gc.rowadd = d->rowadd + c0;
+        if (gc.resid) gc.resid = (const float*)d->resid + c0;
+        if (gc.gate) gc.gate = d->gate_dtype == ASRX_BITS ? (const void*)((const uint32_t*)d->gate + c0 / 32)
+                                                          : (const void*)((const bf16_t*)d->gate + c0);
+        if (gc.mask_out) gc.mask_out = d->mask_out + c0 / 32;
+        const int bn = pl.family == Family::P4 ? 256 : P_BN;
+        run(gc, ((d->m + P_BM - 1) / P_BM) * ((gc.N + bn - 1) / bn));
+      }
+      break;
+    }
+    case Family::Ring64:
+    case Family::Ring128:
+      with_layout(false, pl.bt, [&](auto, auto BT) {
+        if (pl.family == Family::Ring128) dispatch_ring<128, 64, BT>(g, pl.epi, pl.ntiles, batch, st);
+        else dispatch_ring<64, 64, BT>(g, pl.epi, pl.ntiles, batch, st);
+      });
+      break;
+    case Family::TallK:
+      hipLaunchKernelGGL(gemm_bf16_tallk_kernel, dim3(g.splitk), dim3(512), 0, st, g, TallkConv{0, 0, 0, 0, 0, 0});
+      break;
+    case Family::Ws256:
+    case Family::Ws64:
+      launch_ws(g, pl.bt, pl.epi, pl.ntiles, pl.family == Family::Ws64 ? 64 : 256, st);
+      break;
+  }
+  return ASRX_OK;
+}
+
+// Argument checks of asrx_gemm and the kernel arguments every family shares (cvec is the plan's).  An empty problem
+// (m or n = 0) returns ASRX_OK with g.M = 0: nothing to launch.
+int fill_args(const asrx_gemm_desc* d, GemmArgs& g, int& batch) {
+  g = GemmArgs{};
+  if (!d || d->m < 0 || d->n < 0 || d->k < 0 || !d->a || !d->b || !d->c) return ASRX_ERR_ARG;
+  if (d->in_dtype != ASRX_BF16 && d->in_dtype != ASRX_F32) return ASRX_ERR_ARG;
+  if (d->c_dtype != ASRX_BF16 && d->c_dtype != ASRX_F32) return ASRX_ERR_ARG;
+  if (d->m == 0 || d->n == 0) return ASRX_OK;
+  batch = d->batch > 0 ? d->batch : 1;
+  const int splitk = d->splitk > 1 ? d->splitk : 1;
+  if (splitk > 1 && (batch != 1 || !d->workspace || d->workspace_elems < (int64_t)splitk * d->m * d->n))
+    return ASRX_ERR_ARG;
+  if (batch > 65535 || splitk > 65535) return ASRX_ERR_ARG;
+  if (((d->gate && d->gate_dtype == ASRX_BITS) || d->mask_out) && d->in_dtype != ASRX_BF16) return ASRX_ERR_UNSUPPORTED;
+  if (d->rowsum_a && (!d->a_trans || d->in_dtype != ASRX_BF16 || batch != 1)) return ASRX_ERR_UNSUPPORTED;
+  if (d->rowsum_a && splitk > 1 && !d->rowsum_ws) return ASRX_ERR_ARG;
+  g.M = d->m; g.N = d->n; g.K = d->k;
+  g.a = d->a; g.lda = d->lda; g.b = d->b; g.ldb = d->ldb;
+  g.c = d->c; g.ldc = d->ldc; g.c_dtype = d->c_dtype;
+  g.batch_inner = d->batch_inner > 0 ? d->batch_inner : 1;
+  g.sa_o = d->sa_outer; g.sa_i = d->sa_inner; g.sb_o = d->sb_outer; g.sb_i = d->sb_inner;
+  g.sc_o = d->sc_outer; g.sc_i = d->sc_inner;
+  g.alpha = d->alpha; g.beta = d->beta;
+  g.bias = d->bias;
+  g.rowadd = d->rowadd; g.ld_rowadd = d->ld_rowadd; g.rowadd_mod = d->rowadd_mod > 0 ? d->rowadd_mod : 1;
+  g.relu = d->relu;
+  g.drop_thr = drop_threshold(d->dropout_p);
+  g.drop_scale = d->dropout_p > 0.f && d->dropout_p < 1.f ? 1.f / (1.f - d->dropout_p) : 0.f;
+  g.seed = d->seed;
+  g.gate = d->gate; g.ld_gate = d->ld_gate; g.gate_dtype = d->gate_dtype;
+  g.mask_out = d->mask_out; g.ld_mask = d->ld_mask;
+  g.resid = d->resid; g.ld_resid = d->ld_resid; g.resid_dtype = d->resid_dtype;
+  g.ws = d->workspace;
+  g.rowsum = d->rowsum_a;
+  g.rowsum_ws = d->rowsum_ws;
+  g.dbg = gemm_dbg();
+  const int bk = d->in_dtype == ASRX_BF16 ? BK : FBK;   // splits cover whole K-steps
+  g.splitk = splitk;
+  g.k_per_split = ((((int)d->k + bk - 1) / bk + splitk - 1) / splitk) * bk;
+  return ASRX_OK;
+}
+
+// The split-K finish: the partial slabs summed into C through the epilogue, then the row-sum partials.
+int launch_reduce(const GemmArgs& g, Reduce reduce, hipStream_t st) {
+  const int64_t quads = (int64_t)g.M * ((g.N + 3) / 4);
+  if (reduce == Reduce::TallK)
+    hipLaunchKernelGGL(tallk_reduce_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, st, g);
+  else
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)std::min<int64_t>((quads + 255) / 256, 4096)), dim3(256), 0, st, g);
+  ASRX_CHECK_LAUNCH();
+  if (g.rowsum) {
+    hipLaunchKernelGGL(rowsum_finish_kernel, dim3((g.M + 63) / 64), dim3(256), 0, st, g.rowsum_ws, g.splitk, g.M, g.rowsum);
+    ASRX_CHECK_LAUNCH();
+  }
+  return ASRX_OK;
 }
 
 }  // namespace
@@ -1621,178 +1759,41 @@ extern "C" int asrx_gemm_set_debug(int32_t flags) {
 
 extern "C" int asrx_gemm_kernel_name(const asrx_gemm_desc* d, char* buf, int len) {
   if (!d || !buf || len < 8) return ASRX_ERR_ARG;
-  const int batch = d->batch > 0 ? d->batch : 1;
-  const int splitk = d->splitk > 1 ? d->splitk : 1;
-  const char* tf[2] = {"false", "true"};
-  if (d->in_dtype == ASRX_F32) {
-    snprintf(buf, len, "gemm_f32_kernel<%s, %s>", tf[!!d->a_trans], tf[!!d->b_trans]);
-    return ASRX_OK;
-  }
-  const GemmPlan pl = plan_bf16(d, batch, splitk);
-  if (pl.use == 11 || pl.use == 13)
-    snprintf(buf, len, "gemm_bf16_ws_kernel<%s, %d, %d>", tf[!!d->b_trans], pl.epi, pl.use == 13 ? 64 : 256);
-  else if (pl.use == 9)
-    snprintf(buf, len, "gemm_bf16_tallk_kernel");
-  else if (pl.use == 1 || pl.use == 2)
-    snprintf(buf, len, "gemm_bf16_p%d_kernel<%s, %s, %d>", pl.use == 2 ? 4 : 3, tf[!!d->a_trans], tf[!!d->b_trans],
-             pl.use == 2 && (pl.epi == (E_BIAS | E_RELU) || pl.epi == (E_BIAS | E_RELU | E_MASKOUT)) ? pl.epi | E_DROP
-                                                                                                  : pl.epi);
-  else if (pl.use >= 5)
-    snprintf(buf, len, "gemm_bf16_ring_kernel<%d, 64, %s, %s, %d>", pl.use == 6 ? 128 : 64, tf[!!d->a_trans],
-             tf[!!d->b_trans], pl.epi);
+  if (d->in_dtype == ASRX_F32)
+    snprintf(buf, len, "gemm_f32_kernel<%s, %s>", d->a_trans ? "true" : "false", d->b_trans ? "true" : "false");
   else
-    snprintf(buf, len, "gemm_bf16_kernel<%d, %d, %s, %s, %s>", pl.use == 3 ? 128 : 64, pl.use == 3 ? 128 : 64,
-             tf[!!d->a_trans], tf[!!d->b_trans], tf[pl.vec]);
-  return ASRX_OK;
-}
-
-// Enqueue the bf16 plan `pl` (asrx_gemm after argument checks).
-int gemm_bf16_run(const asrx_gemm_desc* d, const GemmArgs& g0, const GemmPlan& pl, int batch, int splitk,
-                  hipStream_t st) {
-  int epi = pl.epi;
-  GemmArgs g = g0;
-  // p4's bias + ReLU (+ mask bits) instantiations without dropout spill registers into the K-loop (the allocator's
-  // margin at ~240 VGPRs; the dropout ones do not): run them as the dropout epilogue with threshold 0 and scale 1 —
-  // every element kept, v * 1.0 = v exactly (eval FFN1 forward 69.9 -> ~57 us alone, round 5)
-  if (pl.use == 2 && (epi == (E_BIAS | E_RELU) || epi == (E_BIAS | E_RELU | E_MASKOUT))) {
-    epi |= E_DROP;
-    g.drop_thr = 0u;
-    g.drop_scale = 1.f;
-  }
-  // the bit-mask output is written only by the paired bf16 store path of the fast epilogues
-  if (d->mask_out && (!(epi != E_GENERIC && (epi & E_MASKOUT)) || !d->relu || d->c_dtype != ASRX_BF16 || d->n % 32 != 0 ||
-                      d->ldc % 8 != 0 || (uintptr_t)d->c % 16 != 0 || (uintptr_t)d->mask_out % 4 != 0 ||
-                      d->ld_mask < d->n / 32))
-    return ASRX_ERR_UNSUPPORTED;
-  if ((pl.use == 1 || pl.use == 2) && (epi & E_BIAS) && epi != E_GENERIC && d->n > P_BIAS_BYTES / 4) {
-    // the p3 bias epilogue stages the whole bias vector in LDS (16 KiB): wider outputs run as column chunks
-    // (fast-path epilogues without dropout only: their element math does not depend on N — the threshold-0 dropout
-    // above keeps every element whatever its hash index)
-    if (((epi & E_DROP) && g.drop_thr != 0u) || d->a_trans || d->b_trans || batch != 1 || splitk != 1) return ASRX_ERR_UNSUPPORTED;
-    for (int c0 = 0; c0 < d->n; c0 += P_BIAS_BYTES / 4) {
-      GemmArgs gc = g;
-      gc.N = std::min(P_BIAS_BYTES / 4, d->n - c0);
-      gc.b = (const bf16_t*)d->b + (int64_t)c0 * d->ldb;
-      gc.bias = d->bias + c0;
-      gc.c = (char*)d->c + (int64_t)c0 * (d->c_dtype == ASRX_F32 ? 4 : 2);
-      if (gc.rowadd) gc.rowadd = d->rowadd + c0;
-      if (gc.resid) gc.resid = (const float*)d->resid + c0;
-      if (gc.gate) gc.gate = d->gate_dtype == ASRX_BITS ? (const void*)((const uint32_t*)d->gate + c0 / 32)
-                                                        : (const void*)((const bf16_t*)d->gate + c0);
-      if (gc.mask_out) gc.mask_out = d->mask_out + c0 / 32;
-      const int bn = pl.use == 2 ? 256 : P_BN;
-      const int nt = ((d->m + P_BM - 1) / P_BM) * ((gc.N + bn - 1) / bn);
-      if (pl.use == 2) dispatch_p3<false, false, true>(gc, epi, nt, 1, 1, st);
-      else dispatch_p3<false, false>(gc, epi, nt, 1, 1, st);
-    }
-  } else if (pl.use == 11 || pl.use == 13) {
-    launch_ws(g, d->b_trans, epi, pl.ntiles, pl.use == 13 ? 64 : 256, st);
-  } else if (pl.use == 9) {
-    hipLaunchKernelGGL(gemm_bf16_tallk_kernel, dim3(splitk), dim3(512), 0, st, g, TallkConv{0, 0, 0, 0, 0, 0});
-  } else if (pl.use == 2) {
-    if (!d->a_trans && !d->b_trans) dispatch_p3<false, false, true>(g, epi, pl.ntiles, splitk, batch, st);
-    else if (!d->a_trans && d->b_trans) dispatch_p3<false, true, true>(g, epi, pl.ntiles, splitk, batch, st);
-    else if (d->a_trans && !d->b_trans) dispatch_p3<true, false, true>(g, epi, pl.ntiles, splitk, batch, st);
-    else dispatch_p3<true, true, true>(g, epi, pl.ntiles, splitk, batch, st);
-  } else if (pl.use == 1) {
-    if (!d->a_trans && !d->b_trans) dispatch_p3<false, false>(g, epi, pl.ntiles, splitk, batch, st);
-    else if (!d->a_trans && d->b_trans) dispatch_p3<false, true>(g, epi, pl.ntiles, splitk, batch, st);
-    else if (d->a_trans && !d->b_trans) dispatch_p3<true, false>(g, epi, pl.ntiles, splitk, batch, st);
-    else dispatch_p3<true, true>(g, epi, pl.ntiles, splitk, batch, st);
-  } else if (pl.use >= 5) {
-    if (!d->b_trans) {
-      if (pl.use == 6) dispatch_ring<128, 64, false, false>(g, epi, splitk, batch, st);
-      else dispatch_ring<64, 64, false, false>(g, epi, splitk, batch, st);
-    } else {
-      if (pl.use == 6) dispatch_ring<128, 64, false, true>(g, epi, splitk, batch, st);
-      else dispatch_ring<64, 64, false, true>(g, epi, splitk, batch, st);
-    }
-  } else if (pl.use == 3) {
-    dispatch_bf16<128, 128>(g, d->a_trans, d->b_trans, pl.vec, batch, st);
-  } else {
-    dispatch_bf16<64, 64>(g, d->a_trans, d->b_trans, pl.vec, batch, st);
-  }
+    plan_name(plan_bf16(d, d->batch > 0 ? d->batch : 1, d->splitk > 1 ? d->splitk : 1), buf, len);
   return ASRX_OK;
 }
 
 static_assert(sizeof(GroupEnt) == sizeof(asrx_gemm_group_dev), "device group table layout");
 
 extern "C" int asrx_gemm(const asrx_gemm_desc* d, void* stream) {
-  if (!d || d->m < 0 || d->n < 0 || d->k < 0 || !d->a || !d->b || !d->c) return ASRX_ERR_ARG;
-  if (d->in_dtype != ASRX_BF16 && d->in_dtype != ASRX_F32) return ASRX_ERR_ARG;
-  if (d->c_dtype != ASRX_BF16 && d->c_dtype != ASRX_F32) return ASRX_ERR_ARG;
-  if (d->m == 0 || d->n == 0) return ASRX_OK;
-  const int batch = d->batch > 0 ? d->batch : 1;
-  const int binner = d->batch_inner > 0 ? d->batch_inner : 1;
-  int splitk = d->splitk > 1 ? d->splitk : 1;
-  if (splitk > 1 && (batch != 1 || !d->workspace || d->workspace_elems < (int64_t)splitk * d->m * d->n))
-    return ASRX_ERR_ARG;
-  if (batch > 65535 || splitk > 65535) return ASRX_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-
   GemmArgs g;
-  g.M = d->m; g.N = d->n; g.K = d->k;
-  g.a = d->a; g.lda = d->lda; g.b = d->b; g.ldb = d->ldb;
-  g.c = d->c; g.ldc = d->ldc; g.c_dtype = d->c_dtype;
-  g.batch_inner = binner;
-  g.sa_o = d->sa_outer; g.sa_i = d->sa_inner; g.sb_o = d->sb_outer; g.sb_i = d->sb_inner;
-  g.sc_o = d->sc_outer; g.sc_i = d->sc_inner;
-  g.alpha = d->alpha; g.beta = d->beta;
-  g.bias = d->bias;
-  g.rowadd = d->rowadd; g.ld_rowadd = d->ld_rowadd; g.rowadd_mod = d->rowadd_mod > 0 ? d->rowadd_mod : 1;
-  g.relu = d->relu;
-  g.drop_thr = drop_threshold(d->dropout_p);
-  g.drop_scale = d->dropout_p > 0.f && d->dropout_p < 1.f ? 1.f / (1.f - d->dropout_p) : 0.f;
-  g.seed = d->seed;
-  g.gate = d->gate; g.ld_gate = d->ld_gate; g.gate_dtype = d->gate_dtype;
-  g.mask_out = d->mask_out; g.ld_mask = d->ld_mask;
-  if (((d->gate && d->gate_dtype == ASRX_BITS) || d->mask_out) && d->in_dtype != ASRX_BF16) return ASRX_ERR_UNSUPPORTED;
-  g.resid = d->resid; g.ld_resid = d->ld_resid; g.resid_dtype = d->resid_dtype;
-  g.ws = d->workspace;
-  g.rowsum = d->rowsum_a;
-  g.rowsum_ws = d->rowsum_ws;
-  g.dbg = gemm_dbg();
-  if (g.rowsum && (!d->a_trans || d->in_dtype != ASRX_BF16 || batch != 1)) return ASRX_ERR_UNSUPPORTED;
-  if (g.rowsum && splitk > 1 && !g.rowsum_ws) return ASRX_ERR_ARG;
-  const int esz = d->c_dtype == ASRX_F32 ? 16 : 8;
-  g.cvec = (d->ldc % 4 == 0) && ((uintptr_t)d->c % esz == 0) && (d->sc_outer % 4 == 0) && (d->sc_inner % 4 == 0);
-
+  int batch = 1;
+  int rc = fill_args(d, g, batch);
+  if (rc != ASRX_OK) return rc;
+  if (g.M == 0) return ASRX_OK;
+  hipStream_t st = (hipStream_t)stream;
+  Reduce reduce = g.splitk > 1 ? Reduce::SplitK : Reduce::None;
   if (d->in_dtype == ASRX_BF16) {
-    const GemmPlan pl = plan_bf16(d, batch, splitk);
-    g.splitk = splitk;
-    g.k_per_split = ((((int)d->k + BK - 1) / BK + splitk - 1) / splitk) * BK;
-    const int rc = gemm_bf16_run(d, g, pl, batch, splitk, st);
+    const GemmPlan pl = plan_bf16(d, batch, g.splitk);
+    g.cvec = pl.cvec;
+    reduce = pl.reduce;
+    rc = launch_plan(d, g, pl, batch, st);
     if (rc != ASRX_OK) return rc;
   } else {
+    g.cvec = c_quads_aligned(d);
     const int vec = (d->lda % 4 == 0) && (d->ldb % 4 == 0) && ((uintptr_t)d->a % 16 == 0) &&
                     ((uintptr_t)d->b % 16 == 0) && (d->sa_outer % 4 == 0) && (d->sa_inner % 4 == 0) &&
                     (d->sb_outer % 4 == 0) && (d->sb_inner % 4 == 0);
-    const int kb = (d->k + FBK - 1) / FBK;
-    g.splitk = splitk;
-    g.k_per_split = ((kb + splitk - 1) / splitk) * FBK;
-    const int ntiles = ((d->m + FBM - 1) / FBM) * ((d->n + FBN - 1) / FBN);
-    dim3 grid(ntiles, splitk, batch);
-    if (!d->a_trans && !d->b_trans) hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, g, vec);
-    else if (!d->a_trans && d->b_trans) hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, dim3(256), 0, st, g, vec);
-    else if (d->a_trans && !d->b_trans) hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(256), 0, st, g, vec);
-    else hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, dim3(256), 0, st, g, vec);
+    const dim3 grid(((d->m + FBM - 1) / FBM) * ((d->n + FBN - 1) / FBN), g.splitk, batch);
+    with_layout(d->a_trans, d->b_trans, [&](auto AT, auto BT) {
+      hipLaunchKernelGGL((gemm_f32_kernel<AT, BT>), grid, dim3(256), 0, st, g, vec);
+    });
   }
   ASRX_CHECK_LAUNCH();
-  if (splitk > 1) {
-    const int64_t quads = (int64_t)d->m * ((d->n + 3) / 4);
-    const int blocks = (int)std::min<int64_t>((quads + 255) / 256, 4096);
-    if (d->in_dtype == ASRX_BF16 && plan_bf16(d, batch, splitk).use == 9)
-      hipLaunchKernelGGL(tallk_reduce_kernel, dim3((unsigned)((quads + 31) / 32)), dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, g);
-    ASRX_CHECK_LAUNCH();
-    if (g.rowsum) {
-      hipLaunchKernelGGL(rowsum_finish_kernel, dim3((d->m + 63) / 64), dim3(256), 0, st, g.rowsum_ws, splitk,
-                         d->m, g.rowsum);
-      ASRX_CHECK_LAUNCH();
-    }
-  }
-  return ASRX_OK;
+  return reduce == Reduce::None ? ASRX_OK : launch_reduce(g, reduce, st);
 }
 
 // The grouped weight gradients of a single-GPU step with AdamW fused into the epilogue (the ws queue launch only:
@@ -1808,7 +1809,7 @@ extern "C" int asrx_gemm_grouped_xcd_adam(const asrx_gemm_desc* common, const as
       (uintptr_t)adam->v | (uintptr_t)adam->g_base) % 16) || (adam->p_bf16 && (uintptr_t)adam->p_bf16 % 8))
     return ASRX_ERR_ARG;
   if (tiles == 0 || blocks == 0) return ASRX_OK;
-  if (common->in_dtype != ASRX_BF16 || !common->a_trans || !common->b_trans || common->tile != 5 ||
+  if (common->in_dtype != ASRX_BF16 || !common->a_trans || !common->b_trans || common->tile != ASRX_GROUP_TILE_WS ||
       common->c_dtype != ASRX_F32 || common->alpha != 1.f || common->beta != 0.f || !common->workspace ||
       common->workspace_elems < 16 || !common->rowsum_ws)
     return ASRX_ERR_UNSUPPORTED;
@@ -1833,19 +1834,19 @@ extern "C" int asrx_gemm_grouped_xcd(const asrx_gemm_desc* common, const asrx_ge
   if (tiles == 0 || blocks == 0) return ASRX_OK;
   if (common->in_dtype != ASRX_BF16 || !common->a_trans || !common->b_trans) return ASRX_ERR_UNSUPPORTED;
   if (common->c_dtype != ASRX_BF16 && common->c_dtype != ASRX_F32) return ASRX_ERR_ARG;
-  if (common->tile == 5) {   // ws: warp-specialised 256x128 tiles (fp32 C, 16-B rows, n % 4 == 0, alpha 1, beta 0|1)
+  if (common->tile == ASRX_GROUP_TILE_WS) {   // ws: warp-specialised 256x128 tiles (fp32 C, 16-B rows, n % 4 == 0, alpha 1, beta 0|1)
     if (common->c_dtype != ASRX_F32 || common->alpha != 1.f ||
         launch_ws_grouped((const GroupEnt*)groups, tile_group, block_tile, tiles, blocks, common->beta, gemm_dbg(),
                           common->workspace && common->workspace_elems >= 16 ? (int*)common->workspace : nullptr,
                           common->workspace && common->workspace_elems >= 16 ? common->rowsum_ws : nullptr,
                           (hipStream_t)stream) != 0)
       return ASRX_ERR_UNSUPPORTED;
-  } else if (common->tile == 3 || common->tile == 4) {   // p3 / p4 LDS-DMA ring tiles, 256x128 / 256x256 (fp32 C, 16-B
-                                                  // rows, n % 4 == 0, alpha 1, beta 0|1)
-    if (launch_p3_grouped(common, (const GroupEnt*)groups, tile_group, block_tile, tiles, blocks, common->tile >= 4,
-                          (hipStream_t)stream) != 0)
+  } else if (common->tile == ASRX_GROUP_TILE_P3 || common->tile == ASRX_GROUP_TILE_P4) {
+    // p3 / p4 LDS-DMA ring tiles, 256x128 / 256x256 (fp32 C, 16-B rows, n % 4 == 0, alpha 1, beta 0|1)
+    if (launch_p3_grouped(common, (const GroupEnt*)groups, tile_group, block_tile, tiles, blocks,
+                          common->tile == ASRX_GROUP_TILE_P4, (hipStream_t)stream) != 0)
       return ASRX_ERR_UNSUPPORTED;
-  } else if (common->tile == 128) {   // register-staged 128x128 tiles (gemm_bf16_tile): any alignment-checked table
+  } else if (common->tile == ASRX_GROUP_TILE_REG) {   // register-staged 128x128 tiles (gemm_bf16_tile): any alignment-checked table
     hipLaunchKernelGGL((gemm_bf16_grouped_dev_kernel<true, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        common->alpha, common->beta, common->c_dtype, common->relu ? 1 : 0, (const GroupEnt*)groups,
                        tile_group, (int)tiles, 0, block_tile);
@@ -1878,11 +1879,5 @@ extern "C" int asrx_conv2_wgrad(const void* dy2, const void* y1, int32_t B, int3
   hipLaunchKernelGGL(gemm_bf16_tallk_kernel, dim3(splitk), dim3(512), 0, st, g,
                      TallkConv{1, F1, T1, F2, T2, y1_bytes});
   ASRX_CHECK_LAUNCH();
-  hipLaunchKernelGGL(tallk_reduce_kernel, dim3((64 * 576 / 4 + 31) / 32), dim3(256), 0, st, g);
-  ASRX_CHECK_LAUNCH();
-  if (db) {
-    hipLaunchKernelGGL(rowsum_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)rws, splitk, 64, db);
-    ASRX_CHECK_LAUNCH();
-  }
-  return ASRX_OK;
+  return launch_reduce(g, Reduce::TallK, st);
 }

@@ -542,6 +542,17 @@ struct GroupEnt {
   int tile_start;   // first global tile index of this group
   int pad;
 };
+// ... as the arguments of one unsplit GEMM with 16-byte aligned C rows (the grouped kernels)
+ASRX_DEV GemmArgs group_args(const GroupEnt& e, float alpha, float beta, int c_dtype, int dbg) {
+  GemmArgs g = {};
+  g.M = e.m; g.N = e.n; g.K = e.k;
+  g.a = e.a; g.lda = e.lda; g.b = e.b; g.ldb = e.ldb; g.c = e.c; g.ldc = e.ldc; g.c_dtype = c_dtype;
+  g.batch_inner = 1; g.alpha = alpha; g.beta = beta; g.rowadd_mod = 1;
+  g.splitk = 1; g.k_per_split = e.k; g.cvec = 1;
+  g.rowsum = e.rowsum;
+  g.dbg = dbg;
+  return g;
+}
 
 template <int TN, int TM>
 ASRX_DEV void keep_live(f4_t (&acc)[TN][TM]) {

@@ -437,13 +437,7 @@ ASRX_DEV void wsg_tile(const GroupEnt* __restrict__ ents, const uint16_t* __rest
   const uint64_t t_start = trace ? __builtin_amdgcn_s_memrealtime() : 0;
   const int gi = __builtin_amdgcn_readfirstlane((int)tile_group[t_all]);
   const GroupEnt e = ents[gi];
-  GemmArgs g = {};
-  g.M = e.m; g.N = e.n; g.K = e.k;
-  g.a = e.a; g.lda = e.lda; g.b = e.b; g.ldb = e.ldb; g.c = e.c; g.ldc = e.ldc; g.c_dtype = ASRX_F32;
-  g.batch_inner = 1; g.alpha = 1.f; g.beta = (EPI & E_BETA) ? 1.f : 0.f; g.rowadd_mod = 1;
-  g.splitk = 1; g.k_per_split = e.k; g.cvec = 1;
-  g.rowsum = e.rowsum;
-  g.dbg = dbg & (9 | 1024);
+  GemmArgs g = group_args(e, 1.f, (EPI & E_BETA) ? 1.f : 0.f, ASRX_F32, dbg & (9 | 1024));
   const int t = t_all - e.tile_start;
   const int ntn = (e.n + WS_BN - 1) / WS_BN;
   // bias-gradient row sums: one column tile per row panel sums every K-step into rowsum (one workgroup per tile),
@@ -513,10 +507,6 @@ ASRX_DEV void wsg_tile(const GroupEnt* __restrict__ ents, const uint16_t* __rest
   }
 }
 
-// Grouped weight gradients dW (+)= dY^T X of every layer in ONE launch on ws tiles: one 256x128 tile per workgroup,
-// block -> tile through block_tile (the host's XCD-aware layout, kernels.xcd_plan) and tile -> group through
-// tile_group; the bias gradient (row sums of dY^T) fused.  Layout-identical table entries to the p3 / p4 grouped
-// kernels (asrx_gemm_group_dev).
 template <int EPI>
 ASRX_DEV void wsg_body(const GroupEnt* __restrict__ ents, const uint16_t* __restrict__ tile_group,
                        const uint16_t* __restrict__ block_tile, int ntiles, int dbg) {
@@ -608,25 +598,15 @@ bool ws_instantiated(bool bt, int epi) {
 int launch_ws_grouped(const GroupEnt* ents, const uint16_t* tile_group, const uint16_t* block_tile, int ntiles,
                       int blocks, float beta, int dbg, int* queue, float* part, hipStream_t st) {
   const dim3 blk(512);
+  if (beta != 0.f && beta != 1.f) return -1;
   if (queue && blocks % 8 == 0) {   // persistent workgroups on per-XCD queues (one per CU, at most 256)
     const int grid = std::min(blocks, 256), depth = blocks / 8;
-    if (beta == 1.f)
-      hipLaunchKernelGGL(gemm_bf16_wsgq_kernel<E_BETA | E_F32>, dim3(grid), blk, 0, st, ents, tile_group, block_tile,
-                         ntiles, depth, queue, part, dbg);
-    else if (beta == 0.f)
-      hipLaunchKernelGGL(gemm_bf16_wsgq_kernel<E_F32>, dim3(grid), blk, 0, st, ents, tile_group, block_tile, ntiles,
-                         depth, queue, part, dbg);
-    else
-      return -1;
+    auto* kernel = beta == 1.f ? gemm_bf16_wsgq_kernel<E_BETA | E_F32> : gemm_bf16_wsgq_kernel<E_F32>;
+    hipLaunchKernelGGL(kernel, dim3(grid), blk, 0, st, ents, tile_group, block_tile, ntiles, depth, queue, part, dbg);
     return 0;
   }
-  if (beta == 1.f)
-    hipLaunchKernelGGL(gemm_bf16_wsg_kernel<E_BETA | E_F32>, dim3(blocks), blk, 0, st, ents, tile_group, block_tile,
-                       ntiles, dbg);
-  else if (beta == 0.f)
-    hipLaunchKernelGGL(gemm_bf16_wsg_kernel<E_F32>, dim3(blocks), blk, 0, st, ents, tile_group, block_tile, ntiles, dbg);
-  else
-    return -1;
+  auto* kernel = beta == 1.f ? gemm_bf16_wsg_kernel<E_BETA | E_F32> : gemm_bf16_wsg_kernel<E_F32>;
+  hipLaunchKernelGGL(kernel, dim3(blocks), blk, 0, st, ents, tile_group, block_tile, ntiles, dbg);
   return 0;
 }
 

@@ -81,14 +81,29 @@ typedef struct asrx_gemm_desc {
    * 16+4q..16+4q+3.  Requires N % 32 == 0, ldc % 8 == 0, 16-B aligned C and the fast fused epilogue; else
    * ASRX_ERR_UNSUPPORTED. */
   uint32_t* mask_out; int64_t ld_mask;
-  /* kernel family (tests / A-B; 0 = auto): 1 = 256x128 LDS-DMA ring (p3), 3 = register-staged tiles, 4 = 64x64
-   * LDS-DMA ring, 5 = 128x64 LDS-DMA ring, 6 = 256x256 LDS-DMA ring (p4), 8 = warp-specialised 256x128 tiles
-   * (ws: 4 MFMA waves + 4 LDS-DMA loader waves; A k-contiguous, N % 128 == 0), 10 = ws on 64x128 tiles (the
-   * 4096-row decoder GEMMs) — honoured where the family's preconditions hold, else auto (codes 9 and 11, round 4's
-   * persistent ws variants, were removed in version 3 and plan as auto).  Every family is a hand-written kernel of
-   * this library. */
+  /* kernel family (tests / A-B), one of the ASRX_GEMM_* codes below — honoured where the family's preconditions
+   * hold, else auto.  Every other value plans as auto too: the retired codes 2, 7, 9, 11 and 12 (9 and 11, round
+   * 4's persistent ws variants, were removed in version 3) and unknown ones.  Every family is a hand-written kernel
+   * of this library. */
   int32_t kernel;
 } asrx_gemm_desc;
+
+/* asrx_gemm_desc.kernel */
+#define ASRX_GEMM_AUTO 0
+#define ASRX_GEMM_P3 1        /* 256x128 LDS-DMA ring */
+#define ASRX_GEMM_REG 3       /* register-staged tiles, 64x64 or 128x128 (asrx_gemm_desc.tile) */
+#define ASRX_GEMM_RING 4      /* 64x64 LDS-DMA ring (A k-contiguous) */
+#define ASRX_GEMM_RING128 5   /* 128x64 LDS-DMA ring (A k-contiguous) */
+#define ASRX_GEMM_P4 6        /* 256x256 LDS-DMA ring */
+#define ASRX_GEMM_WS 8        /* warp-specialised 256x128 tiles (4 MFMA waves + 4 LDS-DMA loader waves; A k-contiguous,
+                               * N % 128 == 0) */
+#define ASRX_GEMM_WS64 10     /* ws on 64x128 tiles (the 4096-row decoder GEMMs) */
+
+/* asrx_gemm_grouped_xcd: common->tile */
+#define ASRX_GROUP_TILE_P3 3     /* p3 LDS-DMA ring, 256x128 tiles */
+#define ASRX_GROUP_TILE_P4 4     /* p4 LDS-DMA ring, 256x256 tiles */
+#define ASRX_GROUP_TILE_WS 5     /* warp-specialised ws kernel, 256x128 tiles */
+#define ASRX_GROUP_TILE_REG 128  /* register-staged 128x128 tiles */
 
 int asrx_gemm(const asrx_gemm_desc* d, void* stream);
 
@@ -107,7 +122,7 @@ typedef struct asrx_gemm_group_dev {
 /* Launch with an explicit workgroup -> tile map: block_tile[b] (device, `blocks` entries, 0xFFFF = idle) names
  * the tile workgroup b computes.  Workgroup b runs on XCD b % 8, so a host that lays the tiles of one group on
  * one XCD at the same time lets them share that XCD's L2 (the operand panels of dW = dY^T X are re-read by
- * every tile of the group).  common->tile selects the tile: 3 = the p3 LDS-DMA ring, 256x128 tiles (m x n;
+ * every tile of the group).  common->tile selects the tile (ASRX_GROUP_TILE_*): 3 = the p3 LDS-DMA ring, 256x128 tiles (m x n;
  * fp32 C with 16-byte aligned rows, every group's n % 4 == 0, alpha 1, beta 0 or 1), 4 = the p4 ring, 256x256
  * tiles (same conditions), 5 = the warp-specialised ws kernel, 256x128 tiles (4 MFMA waves + 4 LDS-DMA loader
  * waves, 3-stage ring; same conditions; with common->workspace set and common->workspace_elems >= 16 it is read
