@@ -156,6 +156,13 @@ SIGNATURES = {
                          c_vp, c_vp],
     "asrx_ctc_greedy": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp],
     "asrx_ctc_workspace_elems": [c_i32, c_i32, c_i32],   # (int64 result: lib() rebinds its restype)
+    "asrx_ctc_prefix_init": [c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "asrx_ctc_prefix_score": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                              c_vp],
+    "asrx_ctc_prefix_advance": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_vp, c_vp],
+    "asrx_beam_step_joint": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64,
+                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes

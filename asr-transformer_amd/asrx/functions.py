@@ -661,7 +661,8 @@ def beam_rank(scores, lengths, length_penalty):
 
 
 @torch.no_grad()
-def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8):
+def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
+                        ctc=None, ctc_weight=0.0):
     """Beam-search decoding on the KV-cached decoder (the reference has none: Decoder.evaluate, model.py:125-151, is
     greedy).  x (B, L0 >= 1) is the prompt, prefilled with teacher forcing; `max_len` new tokens (default seq_len)
     are then chosen with `beam` hypotheses per sample, each step keeping the `beam` best continuations by summed
@@ -674,7 +675,23 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
 
     Everything per step runs on the device (asrx_beam_step picks the slots, asrx_gather_rows reorders the K/V
     caches into their second buffer); the host reads nothing until the end, except every `poll` steps (0 = never)
-    the count of live hypotheses, to stop once all have finished.  Eval only: dropout is off."""
+    the count of live hypotheses, to stop once all have finished.  Eval only: dropout is off.
+
+    ctc_weight = lam in (0, 1] decodes jointly with a CTC head (Watanabe et al. 2017): a hypothesis is ranked by
+    (1 - lam) * log p_att + lam * log p_ctc, the second term the CTC prefix probability of its generated labels, and
+    `scores` are these joint scores.  ctc = (logits, T, blank, input_lengths): the head's fp32 logits [B*T, >= V] of
+    the utterances, their frame count, the blank id and optional int32 frame counts per sample.  Every selecting step
+    then scores the whole vocabulary (asrx_ctc_prefix_score), selects (asrx_beam_step_joint) and advances the
+    survivors' CTC states (asrx_ctc_prefix_advance), all on the device.  The prompt must be one token (the CTC
+    prefix is the generated labels only).  ctc_weight = 0 (default) is the attention-only search, launch for launch."""
+    lam = float(ctc_weight)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1]")
+    if lam > 0.0:
+        if ctc is None:
+            raise RuntimeError("asrx: ctc_weight > 0 needs the CTC head's logits (a model built with ctc=True)")
+        if x.dim() == 2 and x.shape[1] != 1:
+            raise ValueError(f"ctc_weight > 0 takes a one-token prompt, got L0 = {x.shape[1]}")
     C = make_ctx(dec, 0.0)
     C.train, C.p = False, 0.0
     dev = enc_x.device
@@ -723,6 +740,13 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
     n_live = torch.zeros(steps, dtype=torch.int32, device=dev)          # one zeroed word per step
     cur = xr[:, 0].contiguous()
     done = steps
+    prefix = None
+    if lam > 0.0:
+        ctc_logits, ctc_T, ctc_blank, ctc_lengths = ctc
+        if ctc_lengths is not None:
+            ctc_lengths = ctc_lengths.to(device=dev, dtype=torch.int32).contiguous()
+        prefix = K.CtcPrefix(ctc_logits, B, W, int(ctc_T), V, ctc_blank, ctc_lengths)
+        delta = torch.empty(R, Vp, dtype=torch.float32, device=dev)
     for t in range(P):
         xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te)
         s = t - (L0 - 1)
@@ -736,7 +760,13 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
             K.cast(xs, hc)
         lg = torch.empty(R, Vp, dtype=torch.float32, device=dev)
         K.gemm(hc, C.W(cls.weight), lg, R, Vp, d, lda=d, ldb=d, ldc=Vp)
-        K.beam_step(lg, V, B, W, eos, state, other, tok_h[s], par_h[s], src_row, cur=cur, n_live=n_live[s:s + 1])
+        if prefix is None:
+            K.beam_step(lg, V, B, W, eos, state, other, tok_h[s], par_h[s], src_row, cur=cur, n_live=n_live[s:s + 1])
+        else:
+            prefix.score(eos, delta)
+            K.beam_step_joint(lg, V, B, W, eos, delta, 1.0 - lam, lam, state, other, tok_h[s], par_h[s], src_row,
+                              cur=cur, n_live=n_live[s:s + 1])
+            prefix.advance(eos, par_h[s], tok_h[s], state[1])
         state, other = other, state
         if poll and (s + 1) % poll == 0 and s + 1 < steps and int(n_live[s]) == 0:
             done = s + 1
@@ -752,14 +782,27 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
     return BeamResult(tokens, length.long().gather(1, order), score.gather(1, order))
 
 
-def transformer_beam_search(model, spectrum, text=None, **kw):
+def transformer_beam_search(model, spectrum, text=None, ctc_weight=0.0, input_lengths=None, **kw):
     """Transformer.beam_search: front end and encoder as in `evaluate` (model.py:201-206), then
-    decoder_beam_search.  text=None starts every sample on a BOS column (id 1)."""
+    decoder_beam_search.  text=None starts every sample on a BOS column (id 1).  ctc_weight > 0: joint
+    CTC/attention decoding, the one encoder output also feeding the model's CTC head (input_lengths: optional valid
+    encoder frames per sample)."""
+    lam = float(ctc_weight)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1]")
+    if lam > 0.0 and getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("asrx: ctc_weight > 0 needs a model with a CTC head (Transformer(..., ctc=True))")
+    if lam > 0.0 and text is not None and text.dim() == 2 and text.shape[1] != 1:
+        raise ValueError(f"ctc_weight > 0 takes a one-token prompt, got L0 = {text.shape[1]}")
     with torch.no_grad():
         enc = model.encoder(model.input_layer(spectrum))
     if text is None:
         text = torch.ones(spectrum.shape[0], 1, dtype=torch.int64)
-    return decoder_beam_search(model.decoder, text, enc, **kw)
+    if lam == 0.0:
+        return decoder_beam_search(model.decoder, text, enc, **kw)
+    logits, B, T = _ctc_logits_of(model, enc)
+    return decoder_beam_search(model.decoder, text, enc, ctc=(logits, T, model.ctc_blank, input_lengths),
+                               ctc_weight=lam, **kw)
 
 
 @torch.no_grad()
@@ -775,7 +818,12 @@ def transformer_ctc_logits(model, spectrum):
     """Front end and encoder as in `evaluate`, then the CTC head: (fp32 logits [B*T', Vp], B, T')."""
     if getattr(model, "ctc_head", None) is None:
         raise RuntimeError("asrx: the model has no CTC head (build it with Transformer(..., ctc=True))")
-    enc = model.encoder(model.input_layer(spectrum))
+    return _ctc_logits_of(model, model.encoder(model.input_layer(spectrum)))
+
+
+@torch.no_grad()
+def _ctc_logits_of(model, enc):
+    """The CTC head on an encoder output (B, T', d): (fp32 logits [B*T', Vp], B, T')."""
     B, T, d = enc.shape
     C = make_ctx(model, 0.0)
     return ctc_head_fwd(C, model, enc.reshape(B * T, d).to(C.cd).contiguous()), B, T

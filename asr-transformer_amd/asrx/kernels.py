@@ -746,6 +746,73 @@ def beam_step(logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, c
          lo.data_ptr(), _p(n_live), stream())
 
 
+def beam_step_joint(logits, V, B, W, eos, extra, att_weight, extra_weight, state_in, state_out, tok, parent, src_row,
+                    cur=None, n_live=None):
+    """beam_step with a second score per candidate (asrx_beam_step_joint): a live beam's candidate is score +
+    att_weight * log_softmax(logits)[v] + extra_weight * extra[w][v]; extra fp32 [B*W, ld_extra]."""
+    (si, fi, li), (so, fo, lo) = state_in, state_out
+    _cuda(logits, extra, si, fi, li, so, fo, lo, tok, parent, src_row, cur, n_live)
+    R = B * W
+    assert logits.dtype == torch.float32 and logits.shape[0] == R and logits.stride(1) == 1
+    assert extra.dtype == torch.float32 and extra.shape[0] == R and extra.stride(1) == 1 and extra.shape[1] >= V
+    for a, dt in ((si, torch.float32), (so, torch.float32), (fi, torch.uint8), (fo, torch.uint8), (li, torch.int32),
+                  (lo, torch.int32), (tok, torch.int64), (parent, torch.int32), (src_row, torch.int32),
+                  (cur, torch.int64)):
+        assert a is None or (a.dtype == dt and a.numel() == R and a.is_contiguous())
+    assert n_live is None or (n_live.dtype == torch.int32 and n_live.numel() == 1)
+    call("asrx_beam_step_joint", logits.data_ptr(), B, W, V, logits.stride(0), extra.data_ptr(), extra.stride(0),
+         float(att_weight), float(extra_weight), si.data_ptr(), fi.data_ptr(), li.data_ptr(), int(eos), so.data_ptr(),
+         tok.data_ptr(), _p(cur), parent.data_ptr(), src_row.data_ptr(), fo.data_ptr(), lo.data_ptr(), _p(n_live),
+         stream())
+
+
+class CtcPrefix:
+    """Device buffers of CTC prefix scoring for B samples x W beams over T frames (asrx_ctc_prefix_*): the log2
+    softmax table, the frame counts, and two sets of (state [B*W, T, 2], logpsi [B*W], last [B*W]); `cur` is the
+    set that holds the hypotheses' states, `advance` writes the other one and swaps."""
+
+    def __init__(self, logits, B, W, T, V, blank, input_lengths=None):
+        _cuda(logits, input_lengths)
+        assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[0] == B * T
+        assert logits.stride(1) == 1 and logits.shape[1] >= V
+        assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == B
+                                         and input_lengths.is_contiguous())
+        dev = logits.device
+        self.B, self.W, self.T, self.V, self.blank = B, W, T, V, int(blank)
+        self.logp = torch.empty(B * T, V, dtype=torch.float32, device=dev)
+        self.frames = torch.empty(B, dtype=torch.int32, device=dev)
+        R = B * W
+        self.cur, self.alt = ((torch.empty(R, T, 2, dtype=torch.float32, device=dev),
+                               torch.empty(R, dtype=torch.float32, device=dev),
+                               torch.empty(R, dtype=torch.int32, device=dev)) for _ in range(2))
+        st, lpsi, last = self.cur
+        call("asrx_ctc_prefix_init", logits.data_ptr(), B, W, T, V, logits.stride(0), _p(input_lengths), self.blank,
+             self.logp.data_ptr(), self.frames.data_ptr(), st.data_ptr(), lpsi.data_ptr(), last.data_ptr(), stream())
+
+    def score(self, eos, delta):
+        """delta fp32 [B*W, ld >= V] <- the step's CTC score of every continuation (natural log)."""
+        _cuda(delta)
+        assert delta.dtype == torch.float32 and delta.shape[0] == self.B * self.W and delta.stride(1) == 1
+        assert delta.shape[1] >= self.V
+        st, lpsi, last = self.cur
+        call("asrx_ctc_prefix_score", self.logp.data_ptr(), self.frames.data_ptr(), self.B, self.W, self.T, self.V,
+             self.blank, int(eos), st.data_ptr(), lpsi.data_ptr(), last.data_ptr(), delta.data_ptr(), delta.stride(0),
+             stream())
+
+    def advance(self, eos, parent, tok, fin_prev):
+        """The chosen slots' states from their parents' (parent int32 / tok int64 [B*W] of the selection, fin_prev
+        uint8 [B*W] its input flags)."""
+        _cuda(parent, tok, fin_prev)
+        R = self.B * self.W
+        for a, dt in ((parent, torch.int32), (tok, torch.int64), (fin_prev, torch.uint8)):
+            assert a.dtype == dt and a.numel() == R and a.is_contiguous()
+        (si, pi, li), (so, po, lo) = self.cur, self.alt
+        call("asrx_ctc_prefix_advance", self.logp.data_ptr(), self.frames.data_ptr(), self.B, self.W, self.T, self.V,
+             self.blank, int(eos), parent.data_ptr(), tok.data_ptr(), fin_prev.data_ptr(), si.data_ptr(),
+             pi.data_ptr(), li.data_ptr(), so.data_ptr(), po.data_ptr(), lo.data_ptr(), stream())
+        self.cur, self.alt = self.alt, self.cur
+
+
 def gather_rows(src, dst, index, outer, rows, count, row_stride, outer_stride):
     """dst[o][r][:count] = src[o][index[r]][:count] (asrx_gather_rows) over two buffers of one layout (bf16 or
     fp32, strides in elements); index int32 [rows] holds row numbers in [0, rows)."""

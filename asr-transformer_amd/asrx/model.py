@@ -198,10 +198,12 @@ class Decoder(nn.Module):
         from .functions import decoder_evaluate
         return decoder_evaluate(self, x, enc_x)
 
-    def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8):
+    def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
+                    ctc=None, ctc_weight=0.0):
         """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult."""
         from .functions import decoder_beam_search
-        return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll)
+        return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
+                                   ctc_weight)
 
 
 class Transformer(nn.Module):
@@ -242,10 +244,12 @@ class Transformer(nn.Module):
         from .functions import transformer_evaluate
         return transformer_evaluate(self, spectrum, text)
 
-    def beam_search(self, spectrum, text=None, **kw):
-        """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1)."""
+    def beam_search(self, spectrum, text=None, ctc_weight=0.0, input_lengths=None, **kw):
+        """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1).
+        ctc_weight in (0, 1] (ctc=True models): joint CTC/attention decoding, hypotheses ranked by
+        (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc; input_lengths: valid encoder frames per sample."""
         from .functions import transformer_beam_search
-        return transformer_beam_search(self, spectrum, text, **kw)
+        return transformer_beam_search(self, spectrum, text, ctc_weight, input_lengths, **kw)
 
     def ctc_logits(self, spectrum):
         """Front end, encoder and the CTC head (ctc=True models), no grad: fp32 logits (B, T', V)."""

@@ -1,5 +1,6 @@
 // Beam-search decoding on the device: the per-sample top-W over the W x V continuation scores of one decode step
-// (asrx_beam_step) and the reorder of the self-attention K/V caches by the chosen parents (asrx_gather_rows).
+// (asrx_beam_step; asrx_beam_step_joint adds a weighted second score per candidate, the CTC prefix score of
+// ctc_prefix.hip) and the reorder of the self-attention K/V caches by the chosen parents (asrx_gather_rows).
 // The reference decodes greedily only (model.py:125-151); these two serve Decoder.beam_search.
 #include <limits.h>
 
@@ -30,9 +31,23 @@ ASRX_DEV float beam_cand(float score, float logit, float lse) {
   return c != c ? -INFINITY : c;
 }
 
-template <bool LDS>
+// the joint candidate: score + att_w * (logit - lse) + ext_w * extra.  The multiply-adds are explicit so that the LDS
+// and the re-read path round alike whatever the compiler would contract; att_w = 1, ext_w = 0 with extra = 0 is
+// beam_cand bit for bit.
+ASRX_DEV float beam_cand_joint(float score, float logit, float lse, float att_w, float ext_w, float extra) {
+  const float c = __builtin_fmaf(ext_w, extra, __builtin_fmaf(att_w, logit - lse, score));
+  return c != c ? -INFINITY : c;
+}
+
+struct BeamExtra {
+  const float* extra;   // [B*W][ld]: a second score per candidate (JOINT only)
+  int64_t ld;
+  float att_w, ext_w;
+};
+
+template <bool LDS, bool JOINT>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
-    const float* __restrict__ logits, int W, int V, int64_t ld, const float* __restrict__ score_in,
+    const float* __restrict__ logits, int W, int V, int64_t ld, BeamExtra ex, const float* __restrict__ score_in,
     const uint8_t* __restrict__ fin_in, const int32_t* __restrict__ len_in, int eos, float* __restrict__ score_out,
     int64_t* __restrict__ tok_out, int64_t* __restrict__ cur, int32_t* __restrict__ parent_out,
     int32_t* __restrict__ src_row_out, uint8_t* __restrict__ fin_out, int32_t* __restrict__ len_out,
@@ -47,6 +62,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t row0 = (int64_t)blockIdx.x * W;
   const float* x0 = logits + row0 * ld;
+  const float* e0 = JOINT ? ex.extra + row0 * ex.ld : nullptr;
 
   // max-subtracted logsumexp of each live beam's row, one wave per beam
   for (int w = wave; w < W; w += BEAM_WAVES) {
@@ -86,7 +102,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
         const float s = s_score[w];
         c = v == eos ? (s != s ? -INFINITY : s) : __builtin_nanf("");
       } else {
-        c = beam_cand(s_score[w], x0[(int64_t)w * ld + v], s_lse[w]);
+        c = JOINT ? beam_cand_joint(s_score[w], x0[(int64_t)w * ld + v], s_lse[w], ex.att_w, ex.ext_w,
+                                    e0[(int64_t)w * ex.ld + v])
+                  : beam_cand(s_score[w], x0[(int64_t)w * ld + v], s_lse[w]);
       }
       cand[i] = c;
     }
@@ -116,9 +134,10 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
           continue;
         }
         const float* x = x0 + (int64_t)w * ld;
+        const float* e = JOINT ? e0 + (int64_t)w * ex.ld : nullptr;
         const float lse = s_lse[w];
         for (int v = tid; v < V; v += BEAM_THREADS) {
-          const float c = beam_cand(sc, x[v], lse);
+          const float c = JOINT ? beam_cand_joint(sc, x[v], lse, ex.att_w, ex.ext_w, e[v]) : beam_cand(sc, x[v], lse);
           const int i = w * V + v;
           if (beam_before(ps, pi, c, i) && beam_before(c, i, bs, bi)) { bs = c; bi = i; }
         }
@@ -165,10 +184,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
   if (tid == 0 && n_live && live) atomicAdd(n_live, live);
 }
 
-extern "C" int asrx_beam_step(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, const float* score_in,
-                              const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out,
-                              int64_t* tok_out, int64_t* cur, int32_t* parent_out, int32_t* src_row_out,
-                              uint8_t* fin_out, int32_t* len_out, int32_t* n_live, void* stream) {
+template <bool JOINT>
+static int beam_step_launch(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, BeamExtra ex,
+                            const float* score_in, const uint8_t* fin_in, const int32_t* len_in, int64_t eos,
+                            float* score_out, int64_t* tok_out, int64_t* cur, int32_t* parent_out,
+                            int32_t* src_row_out, uint8_t* fin_out, int32_t* len_out, int32_t* n_live, void* stream) {
   if (!logits || !score_in || !fin_in || !len_in || !score_out || !tok_out || !parent_out || !src_row_out ||
       !fin_out || !len_out)
     return ASRX_ERR_ARG;
@@ -181,15 +201,35 @@ extern "C" int asrx_beam_step(const float* logits, int32_t B, int32_t W, int32_t
   hipStream_t st = (hipStream_t)stream;
   const int n = W * V;
   if (n <= BEAM_LDS_CAND)
-    hipLaunchKernelGGL((beam_step_kernel<true>), dim3((unsigned)B), dim3(BEAM_THREADS), (size_t)n * sizeof(float), st,
-                       logits, (int)W, (int)V, ld, score_in, fin_in, len_in, (int)eos, score_out, tok_out, cur,
-                       parent_out, src_row_out, fin_out, len_out, n_live);
+    hipLaunchKernelGGL((beam_step_kernel<true, JOINT>), dim3((unsigned)B), dim3(BEAM_THREADS),
+                       (size_t)n * sizeof(float), st, logits, (int)W, (int)V, ld, ex, score_in, fin_in, len_in,
+                       (int)eos, score_out, tok_out, cur, parent_out, src_row_out, fin_out, len_out, n_live);
   else
-    hipLaunchKernelGGL((beam_step_kernel<false>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, st, logits, (int)W,
-                       (int)V, ld, score_in, fin_in, len_in, (int)eos, score_out, tok_out, cur, parent_out,
+    hipLaunchKernelGGL((beam_step_kernel<false, JOINT>), dim3((unsigned)B), dim3(BEAM_THREADS), 0, st, logits, (int)W,
+                       (int)V, ld, ex, score_in, fin_in, len_in, (int)eos, score_out, tok_out, cur, parent_out,
                        src_row_out, fin_out, len_out, n_live);
   ASRX_CHECK_LAUNCH();
   return ASRX_OK;
+}
+
+extern "C" int asrx_beam_step(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, const float* score_in,
+                              const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out,
+                              int64_t* tok_out, int64_t* cur, int32_t* parent_out, int32_t* src_row_out,
+                              uint8_t* fin_out, int32_t* len_out, int32_t* n_live, void* stream) {
+  return beam_step_launch<false>(logits, B, W, V, ld, BeamExtra{nullptr, 0, 1.f, 0.f}, score_in, fin_in, len_in, eos,
+                                 score_out, tok_out, cur, parent_out, src_row_out, fin_out, len_out, n_live, stream);
+}
+
+extern "C" int asrx_beam_step_joint(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld,
+                                    const float* extra, int64_t ld_extra, float att_weight, float extra_weight,
+                                    const float* score_in, const uint8_t* fin_in, const int32_t* len_in, int64_t eos,
+                                    float* score_out, int64_t* tok_out, int64_t* cur, int32_t* parent_out,
+                                    int32_t* src_row_out, uint8_t* fin_out, int32_t* len_out, int32_t* n_live,
+                                    void* stream) {
+  if (!extra || ld_extra < V || att_weight != att_weight || extra_weight != extra_weight) return ASRX_ERR_ARG;
+  return beam_step_launch<true>(logits, B, W, V, ld, BeamExtra{extra, ld_extra, att_weight, extra_weight}, score_in,
+                                fin_in, len_in, eos, score_out, tok_out, cur, parent_out, src_row_out, fin_out,
+                                len_out, n_live, stream);
 }
 
 // ---- asrx_gather_rows

@@ -33,7 +33,9 @@ extern "C" {
 
 /* Library version / build identification (3: dq_acc holds one slab per key block, asrx_attn_dq_acc_elems;
  * asrx_adam_spans takes bounds that are not multiples of 4.  4: asrx_beam_step and asrx_gather_rows, the device half
- * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy). */
+ * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy.
+ * 6: joint CTC/attention beam search: asrx_ctc_prefix_init, asrx_ctc_prefix_score, asrx_ctc_prefix_advance,
+ * asrx_beam_step_joint). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -479,6 +481,59 @@ int asrx_ctc_targets(const int64_t* text, int64_t ld_text, const float* mask, in
  * host round trip.  T <= 15360. */
 int asrx_ctc_greedy(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int32_t* input_lengths,
                     int32_t blank, int64_t* tok, int32_t* len, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Joint CTC/attention beam search (version >= 6; Watanabe et al. 2017): every hypothesis is ranked by
+ * (1 - lambda) * log p_att(h) + lambda * log p_ctc(h...), the second term the CTC PREFIX probability psi of the
+ * generated labels under the CTC head.  Per decode step: asrx_ctc_prefix_score (all W x V continuations, a reduction
+ * over the frames), asrx_beam_step_joint (selection), asrx_ctc_prefix_advance (the forward state of the W survivors).
+ * Prefix state of slot b*W + w, two sets that the caller ping-pongs like the beam state:
+ *   state   fp32 [B*W][T][2], 8-B aligned: (log2(gn_t + gb_t), log2 gb_t), gn_t / gb_t = the probability of all paths
+ *           over frames 0..t that collapse to the slot's labels and end in a non-blank / in the blank; -inf at t >= T_b
+ *   logpsi  fp32 [B*W]: log2 psi of the slot's labels (0 for the empty prefix)
+ *   last    int32 [B*W]: the last label, -1 for the empty prefix
+ * Everything is fp32 in the log2 domain, every log-sum-exp max-subtracted, no floating-point atomics (the same inputs
+ * give the same bits), no allocation or synchronisation, graph-capturable.  1 <= W <= 16, T >= 1, 0 <= blank < V and
+ * (score / advance) 0 <= eos < V, eos != blank, else ASRX_ERR_ARG before any device access.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* Once per utterance batch (two launches).  logits: the CTC head's fp32 rows b*T + t, row stride ld >= V, columns
+ * [0, V) read; input_lengths: device int32 [B], nullable (T), clamped to [0, T].  Writes logp [B*T][V] = log2 softmax
+ * of every row, frames [B] = T_b, and the empty prefix's state, logpsi = 0 and last = -1 for all B*W slots. */
+int asrx_ctc_prefix_init(const float* logits, int32_t B, int32_t W, int32_t T, int32_t V, int64_t ld,
+                         const int32_t* input_lengths, int32_t blank, float* logp, int32_t* frames, float* state,
+                         float* logpsi, int32_t* last, void* stream);
+
+/* Once per step (one launch): delta[b*W + w][c] (fp32, NATURAL log, row stride ld_delta >= V, columns >= V untouched)
+ * = log psi(g.c) - log psi(g) for an ordinary label c of slot g; the eos column holds the end score
+ * log(gn_{T_b-1}(g) + gb_{T_b-1}(g)) - log psi(g); the blank column holds -inf.  A slot whose psi is 0 gives -inf
+ * everywhere (never NaN).  T_b = 0: -inf for every label, 0 at eos for the empty prefix.  Summed along a finished
+ * hypothesis the terms telescope to its CTC log-likelihood. */
+int asrx_ctc_prefix_score(const float* logp, const int32_t* frames, int32_t B, int32_t W, int32_t T, int32_t V,
+                          int32_t blank, int32_t eos, const float* state, const float* logpsi, const int32_t* last,
+                          float* delta, int64_t ld_delta, void* stream);
+
+/* Once per step after the selection (one launch, one wave per slot): slot j of sample b extends slot parent[j] (int32
+ * in [0, W), asrx_beam_step*'s parent_out) by tok[j] (int64, tok_out).  If the parent had finished (fin_prev [B*W]:
+ * the selection's fin_in) or the token is eos, the parent's state, logpsi and last are copied; otherwise the state of
+ * the extended prefix is built over t < T_b.  The parent gather happens here: *_out must not overlap *_in. */
+int asrx_ctc_prefix_advance(const float* logp, const int32_t* frames, int32_t B, int32_t W, int32_t T, int32_t V,
+                            int32_t blank, int32_t eos, const int32_t* parent, const int64_t* tok,
+                            const uint8_t* fin_prev, const float* state_in, const float* logpsi_in,
+                            const int32_t* last_in, float* state_out, float* logpsi_out, int32_t* last_out,
+                            void* stream);
+
+/* asrx_beam_step with a second score per candidate: a live beam w offers v at
+ * score_in[w] + att_weight * (logits[w][v] - logsumexp(logits[w][:V])) + extra_weight * extra[w][v] (two fused
+ * multiply-adds, fp32; extra fp32 [B*W][ld_extra >= V], columns [0, V) read; NaN reads as -inf).  A finished beam
+ * still offers exactly (w, eos) at score_in[w]; order, outputs, limits and the LDS / re-read paths are those of
+ * asrx_beam_step, which att_weight = 1, extra_weight = 0 over a zero matrix reproduces bit for bit.  The operand is
+ * generic: the CTC prefix scores here, a language model's later. */
+int asrx_beam_step_joint(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, const float* extra,
+                         int64_t ld_extra, float att_weight, float extra_weight, const float* score_in,
+                         const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out, int64_t* tok_out,
+                         int64_t* cur, int32_t* parent_out, int32_t* src_row_out, uint8_t* fin_out, int32_t* len_out,
+                         int32_t* n_live, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
