@@ -587,7 +587,7 @@ def frontend_bwd(C, S, dfeats_c, conv1, conv2):
         K.conv2_wgrad(dy2, S["y1"], gw, G(conv2.bias))
     else:
         C.wgrad(dy2, cols, G(conv2.weight), G(conv2.bias))
-    if cols is None and T1 <= K.CONV_BWD_MAXT1:   # conv2 data gradient never materialised
+    if cols is None and K.conv_bwd_implicit_fits(T):   # conv2 data gradient never materialised
         K.conv_bwd_implicit(dy2, C.W(conv2.weight), S["y1m"], S["x"], G(conv1.weight).view(64, 9), G(conv1.bias))
         return
     dcols = _empty((M2, 576), C.cd, dy2)

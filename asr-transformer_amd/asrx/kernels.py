@@ -922,6 +922,14 @@ def conv2_wgrad(dy2, y1, dw, db, splitk=256):
 
 
 CONV_BWD_MAXT1 = 1024   # frontend.hip CB_MAXT1 (LDS: weights of 6 taps + the row's y1 sign bits + 3 x lines)
+CONV_BWD_MAXLDS = 80 * 1024   # asrx_conv_bwd_implicit's dynamic-LDS ceiling (two workgroups per CU)
+
+
+def conv_bwd_implicit_fits(T):
+    """Whether asrx_conv_bwd_implicit accepts an input of T frames: its T1 cap and its LDS sum (48 KiB of weights +
+    the row's sign bits rounded up to 16 B + three fp32 input lines).  T <= 2048 in effect: the LDS sum binds first."""
+    T1 = (T - 3) // 2 + 1
+    return T1 <= CONV_BWD_MAXT1 and 6 * 64 * 64 * 2 + ((T1 * 8 + 15) & ~15) + 12 * T <= CONV_BWD_MAXLDS
 
 
 def conv_bwd_implicit(dy2, w2, y1_mask, x, dw, db):

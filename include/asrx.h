@@ -321,7 +321,9 @@ int asrx_conv2_wgrad(const void* dy2, const void* y1, int32_t B, int32_t F1, int
  * formed on the fly, neither the column gradient nor dy1 is stored (model.py:168-171 backward).  dy2
  * [B*T2*F2][64] bf16 (ReLU-gated), w2 [64][576] bf16, y1_mask = conv1_fwd's sign bits, x (B,1,F,T) fp32; part:
  * [nblocks + 128][640] workspace, nblocks >= 2 persistent workgroups (about 2/3 take the even-f1 rows).
- * T1 <= 1024 and 48 KiB + T1*8 B + 12*T B of LDS <= 80 KiB. */
+ * Accepted while T1 <= 1024 and 48 KiB + roundup16(T1*8) B + 12*T B of dynamic LDS <= 80 KiB, else
+ * ASRX_ERR_UNSUPPORTED: the LDS sum binds first, T <= 2048 (T1 = 1023, exactly 80 KiB; launches above 64 KiB need no
+ * attribute on gfx950).  asrx.kernels.conv_bwd_implicit_fits mirrors the rule. */
 int asrx_conv_bwd_implicit(const void* dy2, const void* w2, const uint8_t* y1_mask, const float* x, int32_t B, int32_t F,
                            int32_t T, float* part, int32_t nblocks, float* dw, float* db, void* stream);
 int asrx_im2col_conv2(int32_t dtype, const void* y1, int32_t B, int32_t F1, int32_t T1, void* cols, void* stream);

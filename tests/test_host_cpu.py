@@ -438,3 +438,35 @@ def test_device_code_has_no_sgpr_hazard_before_vector_memory():
     two = "global_load_dwordx4 v[2:5], v[0:1], off\nglobal_load_dwordx4 v[6:9], v[0:1], off\ns_waitcnt vmcnt(1)\n"
     assert not asm_hazards.scan_loads(two + "v_mov_b32 v10, v2")
     assert asm_hazards.scan_loads(two + "v_mov_b32 v10, v6")
+
+
+def test_conv_bwd_implicit_gate_mirrors_the_launcher():
+    """kernels.conv_bwd_implicit_fits (blocks.frontend_bwd's choice between the implicit backward and linear_dgrad +
+    conv1_bwd_fused) flips exactly where asrx_conv_bwd_implicit starts to refuse: the T1 cap and the LDS sum are read
+    from frontend.hip, the formula is written out again here.  T = 2049 and 2050 have T1 = 1024 (within the cap) but
+    81,932 and 81,944 B of LDS: a gate on T1 alone sent them to a launcher that refuses them."""
+    from asrx import kernels as K
+    src = open(os.path.join(REPO, "asr-transformer_amd", "csrc", "frontend.hip")).read()
+    maxt1 = int(re.search(r"constexpr int CB_MAXT1 = (\d+);", src).group(1))
+    body = src[src.index('extern "C" int asrx_conv_bwd_implicit('):]
+    body = body[:body.index("hipLaunchKernelGGL")]
+    assert "(size_t)6 * 64 * 64 * 2 + ((T1 * 8 + 15) & ~15) + sizeof(float) * 3 * T" in body
+    assert "if (T1 > CB_MAXT1) return ASRX_ERR_UNSUPPORTED;" in body
+    ceiling = int(re.search(r"shm > (\d+) \* 1024", body).group(1)) * 1024
+    assert (K.CONV_BWD_MAXT1, K.CONV_BWD_MAXLDS) == (maxt1, ceiling)
+
+    def accepted(T):
+        T1 = (T - 3) // 2 + 1
+        return T1 <= maxt1 and 6 * 64 * 64 * 2 + (T1 * 8 + 15) // 16 * 16 + 4 * 3 * T <= ceiling
+
+    got = [K.conv_bwd_implicit_fits(T) for T in range(2040, 2057)]
+    assert got == [accepted(T) for T in range(2040, 2057)]
+    assert got == [T <= 2048 for T in range(2040, 2057)]
+    assert all(K.conv_bwd_implicit_fits(T) == accepted(T) for T in range(7, 4000))
+
+
+def test_frontend_exact_case_stays_exact():
+    """The integer case of tests/test_gpu_frontend.py: every reference is an integer, every accumulator below 2^24 and
+    every bf16 operand or output at most 256 (checked before the case is sent to a GPU)."""
+    from tests import frontend_ref
+    assert frontend_ref.exact_case().check_magnitudes()
