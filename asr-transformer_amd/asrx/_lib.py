@@ -163,6 +163,12 @@ SIGNATURES = {
                                 c_vp, c_vp, c_vp, c_vp, c_vp],
     "asrx_beam_step_joint": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp, c_vp, c_i64,
                              c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "asrx_ctc_prefix_beam": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp,
+                             c_vp, c_vp],
+    "asrx_hyp_tokens": [c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
+                        c_vp],
+    "asrx_seq_logprob": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp],
+    "asrx_rescore_rank": [c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes

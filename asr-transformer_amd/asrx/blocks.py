@@ -472,10 +472,15 @@ def self_attn_bwd(C, S, dy, dy_c, dx_c_out=None, dx_c_p=0.0, dx_c_seed=0):
     return _sublayer_bwd(C, S, dh, dy, dx_c_out, dx_c_p, dx_c_seed)
 
 
-def cross_attn_fwd(C, x, ln, mha, kv, kv_ld, B, L, Te, H):
+def cross_attn_fwd(C, x, ln, mha, kv, kv_ld, B, L, Te, H, group=1):
     """x + Drop(MHA(LN(x), enc)) — no mask (model.py:71); K/V come from the precomputed all-layer projection
-    (kv: this layer's columns of it, kv_ld its row stride)."""
+    (kv: this layer's columns of it, kv_ld its row stride).  group > 1 (forward only): every `group` consecutive
+    sequences of the B share one encoder output (kv holds B / group of them), so the attention runs as batch
+    B / group with group * L queries each; nothing is expanded."""
     assert kv.stride(0) == kv_ld
+    if group != 1:
+        assert B % group == 0 and not C.train
+        B, L = B // group, L * group
     dh = x.shape[1] // H
     prep = attn_prepare(C)
     h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, L, Te, dh)
@@ -532,10 +537,10 @@ def enc_layer_bwd(C, S, dy, dy_c, dx_c_out, dx_c_p=0.0, dx_c_seed=0):
     return self_attn_bwd(C, Sa, dmid, dmid_c, dx_c_out=dx_c_out, dx_c_p=dx_c_p, dx_c_seed=dx_c_seed)
 
 
-def dec_layer_fwd(C, x, layer, B, L, H, spec, kv, kv_ld, Te):
-    """DecoderLayer.forward (model.py:65-75)."""
+def dec_layer_fwd(C, x, layer, B, L, H, spec, kv, kv_ld, Te, group=1):
+    """DecoderLayer.forward (model.py:65-75).  group: see cross_attn_fwd."""
     x1, Sa = self_attn_fwd(C, x, layer._norm1, layer._mask_attention, B, L, H, spec)
-    x2, Sc = cross_attn_fwd(C, x1, layer._norm2, layer._cross_attention, kv, kv_ld, B, L, Te, H)
+    x2, Sc = cross_attn_fwd(C, x1, layer._norm2, layer._cross_attention, kv, kv_ld, B, L, Te, H, group)
     x3, Sf = ffn_fwd(C, x2, layer._norm3, layer._feedforward)
     return x3, (Sa, Sc, Sf)
 

@@ -267,7 +267,10 @@ def _kv_block(C, dec):
     return W.view(n * 2 * d, d), bias, gW.view(n * 2 * d, d), gb
 
 
-def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None):
+def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None, group=1):
+    """Decoder.forward as one native program over B token rows of length L.  group > 1 (eval only): every `group`
+    consecutive rows decode against ONE encoder output, enc_c [(B / group) * Te, d]: self-attention runs as batch B,
+    cross-attention as batch B / group with group * L queries over the once-projected K/V (blocks.cross_attn_fwd)."""
     d, H, n = dec.emb_dim, dec.num_heads, len(dec._layers)
     dev = enc_c.device
     Md = B * L
@@ -281,11 +284,11 @@ def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None)
     s_emb = C.seed()
     K.embed_fwd(text, dec._embedding.weight.data, pe, x, L, C.p, s_emb)
     Wkv, bkv, _, _ = _kv_block(C, dec)
-    kv = torch.empty(B * Te, n * 2 * d, dtype=C.cd, device=dev)
+    kv = torch.empty(B // group * Te, n * 2 * d, dtype=C.cd, device=dev)
     K.linear(enc_c, Wkv, kv, bias=bkv)
     Ss = []
     for l, layer in enumerate(dec._layers):
-        x, S = Bk.dec_layer_fwd(C, x, layer, B, L, H, spec, kv[:, l * 2 * d:], n * 2 * d, Te)
+        x, S = Bk.dec_layer_fwd(C, x, layer, B, L, H, spec, kv[:, l * 2 * d:], n * 2 * d, Te, group)
         Ss.append(S)
     cls = dec._classifier
     if final_norm:
@@ -835,6 +838,164 @@ def transformer_ctc_greedy(model, spectrum, input_lengths=None):
     if input_lengths is not None:
         input_lengths = input_lengths.to(device=logits.device, dtype=torch.int32).contiguous()
     return K.ctc_greedy(logits, model.ctc_head.V, T, model.ctc_blank, input_lengths)
+
+
+# ------------------------------------------------------------------------------------------- two-pass decoding
+
+class RescoreResult(BeamResult):
+    """A BeamResult (tokens, lengths, scores: the same three fields, so it unpacks and indexes alike) that also
+    carries the two terms of the combined score: att_scores and ctc_scores, fp32 (B, nbest)."""
+
+    def __new__(cls, tokens, lengths, scores, att_scores=None, ctc_scores=None):
+        self = super().__new__(cls, tokens, lengths, scores)
+        self.att_scores, self.ctc_scores = att_scores, ctc_scores
+        return self
+
+
+BOS_ID = 1          # the start token of a decode without a prompt (transformer_beam_search's text=None)
+IGNORE_ID = -1      # target id of the positions asrx_seq_logprob leaves out
+
+
+def _rescore_labels(dec, max_len):
+    """max_labels of a two-pass decode: the decoder row holds BOS and the labels, its targets the labels and EOS."""
+    L = min(dec._seq_len if max_len is None else int(max_len), 255)
+    if L < 2:
+        raise ValueError(f"two-pass decoding needs a decoder length >= 2, got {L}")
+    if L > dec._pe.pe[0].shape[0]:
+        raise ValueError(f"decoder length {L} exceeds the PE table ({dec._pe.pe[0].shape[0]}) as in layers.py:73")
+    return L, L - 1
+
+
+def _check_beam(beam, nbest):
+    W, nbest = int(beam), int(nbest)
+    if not 1 <= W <= 16:
+        raise ValueError(f"beam must be in 1..16, got {beam}")
+    if not 1 <= nbest <= W:
+        raise ValueError(f"nbest must be in 1..beam, got {nbest}")
+    return W, nbest
+
+
+def _first_pass(ctc, B, V, W, max_labels, dev):
+    """ctc = (logits, T, blank, input_lengths[, V]): the head's vocabulary is the fifth entry where the caller has the
+    head (the Transformer entries pass it); without it the decoder's V is taken, which a shared vocabulary makes the
+    same."""
+    logits, T, blank, lengths = ctc[:4]
+    V = int(ctc[4]) if len(ctc) > 4 else V
+    if not 0 <= int(blank) < V <= logits.shape[1]:
+        raise ValueError(f"CTC vocabulary {V} / blank {blank} do not fit logits of {logits.shape[1]} columns")
+    if lengths is not None:
+        lengths = lengths.to(device=dev, dtype=torch.int32).contiguous()
+    if logits.shape[0] != B * int(T):
+        raise ValueError(f"CTC logits have {logits.shape[0]} rows, expected B * T = {B * int(T)}")
+    return K.ctc_prefix_beam(logits, V, int(T), int(blank), W, max_labels, lengths)
+
+
+def _words(*ts):
+    """One int32 device vector of the given int32 / fp32 / int64 tensors (a single host copy then reads them all)."""
+    return torch.cat([t.contiguous().view(torch.int32).reshape(-1) for t in ts])
+
+
+def _split(flat, *shapes_dtypes):
+    out, o = [], 0
+    for shape, dt in shapes_dtypes:
+        n = 1
+        for s in shape:
+            n *= s
+        n *= 2 if dt == torch.int64 else 1
+        out.append(flat[o:o + n].view(dt).reshape(shape))
+        o += n
+    return out
+
+
+@torch.no_grad()
+def decoder_ctc_beam_search(dec, ctc, B, beam=8, nbest=1, max_len=None):
+    """The first pass alone (asrx_ctc_prefix_beam): per sample the `nbest` best of `beam` CTC prefix-beam hypotheses.
+    ctc = (logits, T, blank, input_lengths[, V of the head]) as in decoder_beam_search.  BeamResult: tokens (B, nbest, max_labels)
+    int64 labels padded with the blank id, lengths (B, nbest) label counts, scores (B, nbest) fp32 log p_ctc (-inf:
+    fewer hypotheses exist).  One host copy at the end."""
+    W, nbest = _check_beam(beam, nbest)
+    _, max_labels = _rescore_labels(dec, max_len)
+    dev = ctc[0].device
+    tok, lens, score, _ = _first_pass(ctc, B, dec._classifier.V, W, max_labels, dev)
+    flat = _words(tok, lens, score).cpu()
+    tok, lens, score = _split(flat, ((B, W, max_labels), torch.int64), ((B, W), torch.int32), ((B, W), torch.float32))
+    return BeamResult(tok[:, :nbest].clone(), lens[:, :nbest].long(), score[:, :nbest].clone())
+
+
+@torch.no_grad()
+def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None):
+    """Two-pass decoding ("attention rescoring"): asrx_ctc_prefix_beam yields `beam` complete hypotheses per sample
+    from the CTC head's logits alone; ONE teacher-forced decoder forward over all B * beam of them (rows BOS, labels;
+    targets labels, EOS; cross-attention grouped per sample, nothing expanded) gives each log p_att, and they are
+    ranked by log p_att + ctc_weight * log p_ctc.  ctc = (logits, T, blank, input_lengths[, V of the head]);
+    at most min(max_len or seq_len, 255) - 1 labels.  Everything runs on the device in a fixed launch sequence with
+    one host copy at the end.  Returns a RescoreResult filled as beam_search fills a BeamResult: tokens (B, nbest,
+    1 + L) = BOS, labels, EOS..., lengths = labels + 1 (0: no such hypothesis), scores = the combined score, plus
+    att_scores and ctc_scores.  Eval only: dropout is off."""
+    lam = float(ctc_weight)
+    if lam != lam or lam < 0.0:
+        raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
+    if ctc is None:
+        raise RuntimeError("asrx: rescoring needs the CTC head's logits (a model built with ctc=True)")
+    W, nbest = _check_beam(beam, nbest)
+    L, max_labels = _rescore_labels(dec, max_len)
+    C = make_ctx(dec, 0.0)
+    C.train, C.p = False, 0.0
+    dev = enc_x.device
+    B, Te, d = enc_x.shape
+    cls = dec._classifier
+    eos = int(dec._eos_token_id)
+    pad = int(dec.pad_token_id if dec.pad_token_id is not None else 0)
+    if B == 0:
+        z = torch.zeros(0, nbest, dtype=torch.float32)
+        return RescoreResult(torch.zeros(0, nbest, 1 + L, dtype=torch.int64), torch.zeros(0, nbest, dtype=torch.int64),
+                             z, z.clone(), z.clone())
+    R = B * W
+    tok, lens, cscore, n_hyp = _first_pass(ctc, B, cls.V, W, max_labels, dev)
+    dec_in, dec_tgt, mask = K.hyp_tokens(tok, lens, n_hyp, B, W, L, BOS_ID, eos, pad, IGNORE_ID)
+    enc_c = torch.empty(B * Te, d, dtype=C.cd, device=dev)
+    K.cast(enc_x.reshape(B * Te, d).contiguous(), enc_c)
+    logits, _ = decoder_fwd(C, dec, dec_in, mask, enc_c, R, L, Te, final_norm=final_norm, group=W)
+    att = K.seq_logprob(logits, cls.V, dec_tgt, IGNORE_ID, n_hyp, W)
+    score, order = K.rescore_rank(att, cscore, B, W, 1.0, lam)
+    flat = _words(dec_tgt, lens, order, score, att, cscore).cpu()
+    f32, i32 = torch.float32, torch.int32
+    tgt, lens, order, score, att, cscore = _split(flat, ((B, W, L), torch.int64), ((B, W), i32), ((B, W), i32),
+                                                  ((B, W), f32), ((B, W), f32), ((B, W), f32))
+    order = order[:, :nbest].long()
+    live = torch.isfinite(score.gather(1, order))
+    rows = tgt.gather(1, order[:, :, None].expand(-1, -1, L))
+    rows = torch.where(rows == IGNORE_ID, torch.full_like(rows, eos), rows)
+    tokens = torch.cat([torch.full((B, nbest, 1), BOS_ID, dtype=torch.int64), rows], dim=2)
+    lengths = torch.where(live, lens.gather(1, order).long() + 1, torch.zeros(B, nbest, dtype=torch.int64))
+    return RescoreResult(tokens, lengths, score.gather(1, order), att.gather(1, order), cscore.gather(1, order))
+
+
+def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbest=1, max_len=None):
+    """Transformer.ctc_beam_search: front end, encoder, CTC head and the first pass only."""
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("asrx: CTC beam search needs a model with a CTC head (Transformer(..., ctc=True))")
+    _check_beam(beam, nbest)
+    logits, B, T = transformer_ctc_logits(model, spectrum)
+    ctc = (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V)
+    return decoder_ctc_beam_search(model.decoder, ctc, B, beam, nbest, max_len)
+
+
+def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True,
+                        max_len=None):
+    """Transformer.rescore: front end and encoder as in `evaluate`, the CTC head on the one encoder output, then
+    decoder_rescore."""
+    if getattr(model, "ctc_head", None) is None:
+        raise RuntimeError("asrx: rescoring needs a model with a CTC head (Transformer(..., ctc=True))")
+    lam = float(ctc_weight)
+    if lam != lam or lam < 0.0:
+        raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
+    _check_beam(beam, nbest)
+    with torch.no_grad():
+        enc = model.encoder(model.input_layer(spectrum))
+    logits, B, T = _ctc_logits_of(model, enc)
+    return decoder_rescore(model.decoder, enc, (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V), beam,
+                           lam, nbest, final_norm, max_len)
 
 
 # ------------------------------------------------------------------------------------------- sub-modules

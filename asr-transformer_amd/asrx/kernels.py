@@ -1072,6 +1072,74 @@ def ctc_greedy(logits, V, T, blank, input_lengths=None):
     return tok, lens
 
 
+def ctc_prefix_beam(logits, V, T, blank, W, max_labels, input_lengths=None):
+    """CTC prefix beam search of logits fp32 [B*T, ld] (asrx_ctc_prefix_beam), W hypotheses per sample in rank order:
+    (tok int64 [B*W, max_labels] padded with `blank`, len int32 [B*W], score fp32 [B*W] (dead slots: -inf),
+    n_hyp int32 [B])."""
+    _cuda(logits, input_lengths)
+    rows, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld
+    assert T > 0 and rows % T == 0
+    B = rows // T
+    assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == B
+                                     and input_lengths.is_contiguous())
+    dev = logits.device
+    words = B * T * (6 * W + 1)      # the header's workspace rule
+    ws = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    tok = torch.empty(B * W, max_labels, dtype=torch.int64, device=dev)
+    lens = torch.empty(B * W, dtype=torch.int32, device=dev)
+    score = torch.empty(B * W, dtype=torch.float32, device=dev)
+    n_hyp = torch.empty(B, dtype=torch.int32, device=dev)
+    call("asrx_ctc_prefix_beam", logits.data_ptr(), B, T, V, ld, _p(input_lengths), int(blank), int(W),
+         int(max_labels), ws.data_ptr(), words, tok.data_ptr(), lens.data_ptr(), score.data_ptr(), n_hyp.data_ptr(),
+         stream())
+    return tok, lens, score, n_hyp
+
+
+def hyp_tokens(tok, lens, n_hyp, B, W, L, bos, eos, pad, ignore):
+    """Decoder rows of the first pass's hypotheses (asrx_hyp_tokens): (dec_in int64 [B*W, L], dec_tgt int64 [B*W, L],
+    mask fp32 [B*W, L])."""
+    _cuda(tok, lens, n_hyp)
+    R = B * W
+    assert tok.dtype == torch.int64 and tok.dim() == 2 and tok.shape[0] == R and tok.stride(1) == 1
+    assert lens.dtype == torch.int32 and lens.numel() == R and lens.is_contiguous()
+    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() == B and n_hyp.is_contiguous())
+    dev = tok.device
+    dec_in = torch.empty(R, L, dtype=torch.int64, device=dev)
+    dec_tgt = torch.empty(R, L, dtype=torch.int64, device=dev)
+    mask = torch.empty(R, L, dtype=torch.float32, device=dev)
+    call("asrx_hyp_tokens", tok.data_ptr(), tok.stride(0), lens.data_ptr(), _p(n_hyp), B, W, L, int(bos), int(eos),
+         int(pad), int(ignore), dec_in.data_ptr(), dec_tgt.data_ptr(), mask.data_ptr(), stream())
+    return dec_in, dec_tgt, mask
+
+
+def seq_logprob(logits, V, tgt, ignore, n_hyp=None, W=1):
+    """Summed log-probability of each target row (asrx_seq_logprob): logits fp32 [N*L, ld], tgt int64 [N, L] ->
+    fp32 [N]; positions with target `ignore` do not count, dead slots (n_hyp, W) give -inf."""
+    _cuda(logits, tgt, n_hyp)
+    N, L = tgt.shape
+    assert logits.dtype == torch.float32 and logits.shape[0] == N * L and logits.stride(1) == 1
+    assert logits.shape[1] >= V and tgt.dtype == torch.int64 and tgt.is_contiguous()
+    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() * W == N and n_hyp.is_contiguous())
+    out = torch.empty(N, dtype=torch.float32, device=logits.device)
+    call("asrx_seq_logprob", logits.data_ptr(), N, L, V, logits.stride(0), tgt.data_ptr(), int(ignore), _p(n_hyp),
+         int(W), out.data_ptr(), stream())
+    return out
+
+
+def rescore_rank(att, ctc, B, W, att_weight, ctc_weight):
+    """(score fp32 [B*W] = att_weight * att + ctc_weight * ctc by slot, order int32 [B, W] = slots best first)
+    (asrx_rescore_rank)."""
+    _cuda(att, ctc)
+    for a in (att, ctc):
+        assert a.dtype == torch.float32 and a.numel() == B * W and a.is_contiguous()
+    score = torch.empty(B * W, dtype=torch.float32, device=att.device)
+    order = torch.empty(B, W, dtype=torch.int32, device=att.device)
+    call("asrx_rescore_rank", att.data_ptr(), ctc.data_ptr(), B, W, float(att_weight), float(ctc_weight),
+         score.data_ptr(), order.data_ptr(), stream())
+    return score, order
+
+
 def adam(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, decoupled=False, hyp=None):
     """Fused Adam/AdamW step `step` (1-based).  hyp (optional fp32 device [3]): lr and bias corrections read by
     the kernel at run time (a replayed HIP graph; see adam_hyper)."""

@@ -205,6 +205,12 @@ class Decoder(nn.Module):
         return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
                                    ctc_weight)
 
+    def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None):
+        """Two-pass decoding from an encoder output and its CTC logits, ctc = (logits, T, blank, input_lengths) as in
+        beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult."""
+        from .functions import decoder_rescore
+        return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len)
+
 
 class Transformer(nn.Module):
     """model.py:154-206.  forward(spectrum (B,1,F,T), text (B,L) int, mask (B,L)) -> logits (B,L,V)."""
@@ -263,3 +269,19 @@ class Transformer(nn.Module):
         (B, T') int64 left-packed and padded with the blank id, lengths (B,) int32), both on the device."""
         from .functions import transformer_ctc_greedy
         return transformer_ctc_greedy(self, spectrum, input_lengths)
+
+    def ctc_beam_search(self, spectrum, beam=8, input_lengths=None, nbest=1):
+        """CTC prefix beam search without the decoder (ctc=True models): front end, encoder, head, then the whole
+        search in one launch (asrx_ctc_prefix_beam).  Returns a BeamResult: tokens (B, nbest, max_labels) int64 labels
+        padded with the blank id, lengths (B, nbest) label counts, scores (B, nbest) fp32 log p_ctc, best first;
+        max_labels = min(decoder seq_len, 255) - 1."""
+        from .functions import transformer_ctc_beam_search
+        return transformer_ctc_beam_search(self, spectrum, beam, input_lengths, nbest)
+
+    def rescore(self, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True, max_len=None):
+        """Two-pass decoding (ctc=True models): ctc_beam_search's `beam` hypotheses, one teacher-forced decoder forward
+        over all of them, ranked by log p_att + ctc_weight * log p_ctc.  Returns a RescoreResult: a BeamResult
+        filled as beam_search fills it (tokens BOS, labels, EOS...; lengths count the EOS; scores combined) with
+        att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample (the CTC frames only)."""
+        from .functions import transformer_rescore
+        return transformer_rescore(self, spectrum, beam, ctc_weight, input_lengths, nbest, final_norm, max_len)

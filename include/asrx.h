@@ -35,7 +35,8 @@ extern "C" {
  * asrx_adam_spans takes bounds that are not multiples of 4.  4: asrx_beam_step and asrx_gather_rows, the device half
  * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy.
  * 6: joint CTC/attention beam search: asrx_ctc_prefix_init, asrx_ctc_prefix_score, asrx_ctc_prefix_advance,
- * asrx_beam_step_joint). */
+ * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
+ * asrx_rescore_rank). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -536,6 +537,50 @@ int asrx_beam_step_joint(const float* logits, int32_t B, int32_t W, int32_t V, i
                          const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out, int64_t* tok_out,
                          int64_t* cur, int32_t* parent_out, int32_t* src_row_out, uint8_t* fin_out, int32_t* len_out,
                          int32_t* n_live, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Two-pass decoding (version >= 7; "attention rescoring"): CTC prefix beam search over the encoder frames yields W
+ * complete hypotheses per utterance without the decoder, ONE teacher-forced decoder forward over all B*W of them
+ * gives each its attention log-probability, and they are re-ranked by att_weight * log p_att + ctc_weight * log p_ctc.
+ * ------------------------------------------------------------------------------------------------- */
+/* The whole first pass in one launch, one workgroup per utterance.  logits as for asrx_ctc_greedy (fp32 rows b*T + t,
+ * row stride ld >= V, columns [0, V) read; input_lengths device int32 [B], nullable, clamped to [0, T]).  Prefix
+ * beam search over the full vocabulary (no per-frame token pruning) with W in 1..16 hypotheses of at most
+ * max_labels >= 1 labels: a
+ * hypothesis g carries (pb, pnb), the log-probability of the paths so far that collapse to g and end in the blank /
+ * in a non-blank; per frame its stay (with the mass of its parent's extension, if the parent is in the beam) and its
+ * extensions by every non-blank column compete, and the W best by log(pb + pnb) survive under asrx_beam_step's total
+ * order (score descending, flat index w*V + c ascending, NaN read as -inf; -inf is never selected, so fewer than W
+ * may live).  A prefix is known by a 64-bit hash of its label string (a prefix that is pruned and selected again
+ * later is the same prefix to its children that stayed; two different strings of one beam collide with probability
+ * about 2^-64 per pair).  One departure from the order above: two DIFFERENT logits of a frame whose candidate scores
+ * round to the same fp32 value are taken larger logit first, not lower column first (equal logits: lower column
+ * first), so among equal scores at the boundary the survivor may differ from the flat-index rule's.
+ * fp32, every frame renormalised by its best score with the offset kept in a double; deterministic.
+ * Outputs per slot b*W + j in final rank order, dead slots last: tok int64 [B*W][max_labels] (the rest = blank),
+ * len int32, score fp32 = log(pb + pnb) after the last frame in natural-log units (dead: len 0, score -inf), n_hyp
+ * int32 [B] = the live count.  No frames (T_b = 0): one hypothesis, the empty prefix, score 0.
+ * ws: device workspace of ws_words >= B * T * (6 * W + 1) 4-byte words, 4-byte aligned (per frame the row's
+ * logsumexp and its 2W best columns, and the trie of the selected extensions that the final phase walks back).
+ * ASRX_ERR_ARG for W outside 1..16, T <= 0, blank outside [0, V), max_labels < 1, before any device access. */
+int asrx_ctc_prefix_beam(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld,
+                         const int32_t* input_lengths, int32_t blank, int32_t W, int32_t max_labels, void* ws,
+                         int64_t ws_words, int64_t* tok, int32_t* len, float* score, int32_t* n_hyp, void* stream);
+/* Decoder-ready rows of width L from the first pass (tok row stride ld_tok; n = min(len, L - 1)): dec_in = bos, the n
+ * labels, pad...; dec_tgt = the n labels, eos, ignore...; mask (float) = 1 over the first n + 1 positions.  A dead
+ * slot (j >= n_hyp[b]; n_hyp nullable) is all pad / all ignore with mask 0.  One launch. */
+int asrx_hyp_tokens(const int64_t* tok, int64_t ld_tok, const int32_t* len, const int32_t* n_hyp, int32_t B, int32_t W,
+                    int32_t L, int64_t bos, int64_t eos, int64_t pad, int64_t ignore, int64_t* dec_in,
+                    int64_t* dec_tgt, float* mask, void* stream);
+/* out[n] = sum over positions i, in order, of logits[n*L + i][tgt[n][i]] - logsumexp(logits[n*L + i][0 .. V)) where
+ * tgt[n][i] != ignore (fp32 rows of stride ld; a target outside [0, V) is skipped too).  With n_hyp (int32
+ * [N / W], nullable) sequence n = b*W + j is dead for j >= n_hyp[b]: out = -inf, its rows are not read. */
+int asrx_seq_logprob(const float* logits, int32_t N, int32_t L, int32_t V, int64_t ld, const int64_t* tgt,
+                     int64_t ignore, const int32_t* n_hyp, int32_t W, float* out, void* stream);
+/* score[b*W + j] = att_weight * att + ctc_weight * ctc (-inf where either term is -inf or the sum is NaN) and
+ * order[b][r] (int32 [B][W]) = the slot of rank r under the total order above (score descending, slot ascending). */
+int asrx_rescore_rank(const float* att, const float* ctc, int32_t B, int32_t W, float att_weight, float ctc_weight,
+                      float* score, int32_t* order, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
