@@ -169,6 +169,9 @@ SIGNATURES = {
                         c_vp],
     "asrx_seq_logprob": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp],
     "asrx_rescore_rank": [c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp],
+    "asrx_ctc_align": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
+                       c_vp, c_vp, c_vp, c_vp, c_vp],
+    "asrx_ctc_align_workspace_words": [c_i32, c_i32, c_i32],   # (int64 result: lib() rebinds its restype)
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
@@ -198,6 +201,8 @@ def lib():
         L.asrx_attn_dq_acc_elems.restype = c_i64
         L.asrx_ctc_workspace_elems.argtypes = [c_i32, c_i32, c_i32]
         L.asrx_ctc_workspace_elems.restype = c_i64
+        L.asrx_ctc_align_workspace_words.argtypes = [c_i32, c_i32, c_i32]
+        L.asrx_ctc_align_workspace_words.restype = c_i64
         _lib = L
     return _lib
 

@@ -840,6 +840,30 @@ def transformer_ctc_greedy(model, spectrum, input_lengths=None):
     return K.ctc_greedy(logits, model.ctc_head.V, T, model.ctc_blank, input_lengths)
 
 
+@torch.no_grad()
+def transformer_align(model, spectrum, text, mask=None, input_lengths=None, *, bos_token_id=1):
+    """Transformer.align: front end, encoder and CTC head, the transcript's CTC targets as the Trainer builds them
+    (asrx_ctc_targets: `text` (B, n) where mask >= 1, without BOS / EOS / PAD), then asrx_ctc_align."""
+    logits, B, T = transformer_ctc_logits(model, spectrum)
+    dev = logits.device
+    dec = model.decoder
+    drop = [int(bos_token_id), int(dec._eos_token_id)]
+    if dec.pad_token_id is not None:
+        drop.append(int(dec.pad_token_id))
+    text = text.to(device=dev, dtype=torch.int64)
+    if text.dim() != 2 or text.shape[0] != B:
+        raise ValueError(f"text {tuple(text.shape)} does not hold one row for each of the {B} spectrograms")
+    if mask is None:
+        mask = torch.ones_like(text) if dec.pad_token_id is None else text != int(dec.pad_token_id)
+    targets, lengths = K.ctc_targets(text if text.stride(1) == 1 else text.contiguous(),
+                                     mask.to(device=dev, dtype=torch.float32).contiguous(), drop, model.ctc_blank)
+    if input_lengths is not None:
+        input_lengths = input_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    # (a row longer than the kernel's 255 labels has no alignment there: its score is -inf)
+    return K.ctc_align(logits, model.ctc_head.V, T, targets, lengths, input_lengths,
+                       max_target_len=min(targets.shape[1], 255), blank=model.ctc_blank)
+
+
 # ------------------------------------------------------------------------------------------- two-pass decoding
 
 class RescoreResult(BeamResult):

@@ -3,6 +3,7 @@ HIP stream; every call goes to the native library (no CPU / PyTorch fallback).""
 import ctypes
 import os
 import math
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -1094,6 +1095,68 @@ def ctc_prefix_beam(logits, V, T, blank, W, max_labels, input_lengths=None):
          int(max_labels), ws.data_ptr(), words, tok.data_ptr(), lens.data_ptr(), score.data_ptr(), n_hyp.data_ptr(),
          stream())
     return tok, lens, score, n_hyp
+
+
+class CtcAlignment(NamedTuple):
+    """Forced alignment of a batch (ctc_align): frame_pos int32 [B, T] (target position per frame, -1 = blank or past
+    the input length), frame_logp fp32 [B, T], start / end int32 [B, Lmax] (label u's frames [start, end); -1 past
+    the target length), conf fp32 [B, Lmax] (exp of the run's mean log-probability), score fp32 [B] (the path's
+    log-probability; -inf = the transcript has no alignment); targets / target_lengths: the labels that were aligned
+    (position u of sample b is token targets[b, u])."""
+    frame_pos: torch.Tensor
+    frame_logp: torch.Tensor
+    start: torch.Tensor
+    end: torch.Tensor
+    conf: torch.Tensor
+    score: torch.Tensor
+    targets: Optional[torch.Tensor] = None
+    target_lengths: Optional[torch.Tensor] = None
+
+
+def ctc_align_workspace_words(B, T, max_target_len):
+    """4-byte workspace words of ctc_align (asrx_ctc_align_workspace_words: the C-ABI's own size rule)."""
+    from ._lib import lib
+    n = lib().asrx_ctc_align_workspace_words(B, T, max_target_len)
+    if n < 0:
+        raise RuntimeError(f"asrx: no alignment workspace for B {B}, T {T}, max target length {max_target_len}")
+    return n
+
+
+def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_target_len=None, blank=0):
+    """Best CTC path of logits fp32 [B*T, ld] (rows b*T + t; asrx_ctc_align, log-softmax fused) that collapses to
+    targets int64 [B, >= max_target_len] of target_lengths int32 [B]; frames t >= input_lengths[b] (int32 [B], None =
+    T) are ignored.  max_target_len is the host-side bound of the lengths (default: the targets' width, at most 255).
+    Returns a CtcAlignment; nothing leaves the device."""
+    _cuda(logits, targets, target_lengths, input_lengths)
+    rows, ld = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
+        "asrx: ctc_align needs contiguous fp32 logits [B*T, ld]"
+    assert T > 0 and rows % T == 0
+    B = rows // T
+    assert targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[0] == B
+    assert targets.shape[1] == 0 or targets.stride(1) == 1
+    if max_target_len is None:
+        max_target_len = targets.shape[1]
+    assert max_target_len <= targets.shape[1]
+    for a in (target_lengths, input_lengths):
+        assert a is None or (a.dtype == torch.int32 and a.numel() == B and a.is_contiguous())
+    dev = logits.device
+    lmax = max(max_target_len, 0)
+    # (the size rule refuses what the call refuses: let the call report a too long target)
+    words = ctc_align_workspace_words(B, T, min(lmax, 255))
+    ws = torch.empty(words, dtype=torch.int32, device=dev)
+    frame_pos = torch.empty(B, T, dtype=torch.int32, device=dev)
+    frame_logp = torch.empty(B, T, dtype=torch.float32, device=dev)
+    start = torch.empty(B, lmax, dtype=torch.int32, device=dev)
+    end = torch.empty(B, lmax, dtype=torch.int32, device=dev)
+    conf = torch.empty(B, lmax, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    tgt_stride = targets.stride(0) if targets.shape[1] else 0
+    call("asrx_ctc_align", logits.data_ptr(), B, T, V, ld, targets.data_ptr() if targets.numel() else None, tgt_stride,
+         _p(input_lengths), target_lengths.data_ptr(), max_target_len, blank, ws.data_ptr(), words,
+         frame_pos.data_ptr(), frame_logp.data_ptr(), start.data_ptr() if lmax else None,
+         end.data_ptr() if lmax else None, conf.data_ptr() if lmax else None, score.data_ptr(), stream())
+    return CtcAlignment(frame_pos, frame_logp, start, end, conf, score, targets, target_lengths)
 
 
 def hyp_tokens(tok, lens, n_hyp, B, W, L, bos, eos, pad, ignore):

@@ -270,6 +270,19 @@ class Transformer(nn.Module):
         from .functions import transformer_ctc_greedy
         return transformer_ctc_greedy(self, spectrum, input_lengths)
 
+    def align(self, spectrum, text, mask=None, input_lengths=None):
+        """Forced alignment without the decoder (ctc=True models): the best CTC path through the T' encoder frames
+        that collapses to the transcript, on the device (asrx_ctc_align).  text: (B, n) token ids, of which the
+        positions with mask >= 1 (None: text != pad) that are not BOS / EOS / PAD are the labels, as in training;
+        input_lengths: (B,) valid encoder frames (None: all T').  Returns a CtcAlignment, all on the device:
+        frame_pos (B, T') int32 label position per frame (-1: blank), frame_logp (B, T') fp32, start / end (B, Lmax)
+        int32 frames [start, end) of each label (asrx.frame_span maps them to spectrogram frames), conf (B, Lmax) fp32
+        per-label confidence, score (B,) fp32 log-probability of the path (-inf: the transcript cannot be aligned, for
+        instance more labels than frames), and targets (B, n) int64 / target_lengths (B,) int32, which map a position
+        back to its token id."""
+        from .functions import transformer_align
+        return transformer_align(self, spectrum, text, mask, input_lengths)
+
     def ctc_beam_search(self, spectrum, beam=8, input_lengths=None, nbest=1):
         """CTC prefix beam search without the decoder (ctc=True models): front end, encoder, head, then the whole
         search in one launch (asrx_ctc_prefix_beam).  Returns a BeamResult: tokens (B, nbest, max_labels) int64 labels

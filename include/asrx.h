@@ -36,7 +36,7 @@ extern "C" {
  * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy.
  * 6: joint CTC/attention beam search: asrx_ctc_prefix_init, asrx_ctc_prefix_score, asrx_ctc_prefix_advance,
  * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
- * asrx_rescore_rank). */
+ * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -581,6 +581,42 @@ int asrx_seq_logprob(const float* logits, int32_t N, int32_t L, int32_t V, int64
  * order[b][r] (int32 [B][W]) = the slot of rank r under the total order above (score descending, slot ascending). */
 int asrx_rescore_rank(const float* att, const float* ctc, int32_t B, int32_t W, float att_weight, float ctc_weight,
                       float* score, int32_t* order, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Forced alignment (version >= 8): the best CTC path through the frames that collapses to a given transcript, and
+ * from it per-frame positions, per-token frame spans and confidences.
+ * ------------------------------------------------------------------------------------------------- */
+/* 4-byte words of workspace asrx_ctc_align needs: 2 * B * T (every row's logsumexp, the path's states), and for
+ * T > 1008, where the backpointers no longer fit in LDS, 32 * B * T more.  Host-only arithmetic; -1 on bad arguments
+ * (B <= 0, T <= 0, max_target_len outside [0, 255]). */
+int64_t asrx_ctc_align_workspace_words(int32_t B, int32_t T, int32_t max_target_len);
+/* Inputs and limits are asrx_ctc_loss's: fp32 logits rows b*T + t of stride ld >= V (the log-softmax is fused:
+ * lp[t][c] = logits[t][c] - logsumexp(logits[t][0 .. V))), targets int64 [B][tgt_stride >= max_target_len],
+ * input_lengths nullable and clamped to [0, T], target_lengths int32 [B]; max_target_len > 255 returns
+ * ASRX_ERR_UNSUPPORTED, blank outside [0, V), T <= 0 or B <= 0 ASRX_ERR_ARG, all before any device access.
+ * Over the extended states s in [0, 2L] (even: blank, odd 2u + 1: label u):
+ *   a[0][0] = lp[0][blank], a[0][1] = lp[0][y_0], -inf elsewhere,
+ *   a[t][s] = lp[t][ext_s] + max(a[t-1][s], a[t-1][s-1], a[t-1][s-2]), s - 2 only for an odd s with ext_s != ext_{s-2};
+ * ties: the skip s - 2 only if strictly greater than both others, else s - 1 only if strictly greater than the stay;
+ * the path ends in state 2L only if a[T_b-1][2L] > a[T_b-1][2L-1] (L = 0: state 0) and is the backtrace from there.
+ * Outputs (all of every one written by every call; Lmax = max_target_len):
+ *   frame_pos   int32 [B][T]     target position u emitted at frame t < T_b, -1 for the blank and for t >= T_b
+ *   frame_logp  fp32  [B][T]     lp[t][emitted symbol], 0 for t >= T_b
+ *   tok_start / tok_end  int32 [B][Lmax]   first frame and one past the last frame of label u's run; -1 for u >= L_b
+ *   tok_conf    fp32  [B][Lmax]  exp(mean of frame_logp over the run), summed in frame order; 0 for u >= L_b
+ *   score       fp32  [B]        the path's log-probability (natural log)
+ * No alignment (T_b < L_b + the number of adjacent equal labels; a target length outside [0, max_target_len]; a label
+ * that is the blank or outside [0, V), which is never used as an index; no path of finite score): score = -inf,
+ * frame_pos all -1, frame_logp all 0, the token outputs -1 / -1 / 0.  L_b = 0 with T_b = 0: the empty alignment,
+ * score 0.  One wave64 per sample after a row-parallel logsumexp launch; the states are renormalised every four
+ * frames with the offset kept in a double; backpointers (3 bits per (blank, label) pair and frame) in LDS while
+ * T <= 1008, in ws above.  ws: asrx_ctc_align_workspace_words() 4-byte words, 4-byte aligned, contents undefined
+ * after the call.  No host round trip, no allocation, graph-capturable, deterministic. */
+int asrx_ctc_align(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int64_t* targets,
+                   int64_t tgt_stride, const int32_t* input_lengths, const int32_t* target_lengths,
+                   int32_t max_target_len, int32_t blank, void* ws, int64_t ws_words, int32_t* frame_pos,
+                   float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score,
+                   void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
