@@ -172,9 +172,13 @@ SIGNATURES = {
     "asrx_ctc_align": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp,
                        c_vp, c_vp, c_vp, c_vp, c_vp],
     "asrx_ctc_align_workspace_words": [c_i32, c_i32, c_i32],   # (int64 result: lib() rebinds its restype)
+    "asrx_edit_distance": [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32,
+                           c_i64, c_vp, c_vp, c_vp],
+    "asrx_mbr_rank": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
+ED_PAIRS, ED_GROUP, ED_CROSS = 0, 1, 2    # asrx_edit_distance pairing modes
 CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended states)
 
 ERRORS = {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}

@@ -868,11 +868,13 @@ def transformer_align(model, spectrum, text, mask=None, input_lengths=None, *, b
 
 class RescoreResult(BeamResult):
     """A BeamResult (tokens, lengths, scores: the same three fields, so it unpacks and indexes alike) that also
-    carries the two terms of the combined score: att_scores and ctc_scores, fp32 (B, nbest)."""
+    carries the two terms of the combined score: att_scores and ctc_scores, fp32 (B, nbest), and, where the order is
+    a minimum-Bayes-risk one (rescore(mbr_scale=...), asrx.mbr_rerank), `risks`: each hypothesis's expected edit
+    distance under the n-best posterior, fp32 (B, nbest), else None."""
 
-    def __new__(cls, tokens, lengths, scores, att_scores=None, ctc_scores=None):
+    def __new__(cls, tokens, lengths, scores, att_scores=None, ctc_scores=None, risks=None):
         self = super().__new__(cls, tokens, lengths, scores)
-        self.att_scores, self.ctc_scores = att_scores, ctc_scores
+        self.att_scores, self.ctc_scores, self.risks = att_scores, ctc_scores, risks
         return self
 
 
@@ -947,7 +949,7 @@ def decoder_ctc_beam_search(dec, ctc, B, beam=8, nbest=1, max_len=None):
 
 
 @torch.no_grad()
-def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None):
+def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None):
     """Two-pass decoding ("attention rescoring"): asrx_ctc_prefix_beam yields `beam` complete hypotheses per sample
     from the CTC head's logits alone; ONE teacher-forced decoder forward over all B * beam of them (rows BOS, labels;
     targets labels, EOS; cross-attention grouped per sample, nothing expanded) gives each log p_att, and they are
@@ -955,10 +957,19 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     at most min(max_len or seq_len, 255) - 1 labels.  Everything runs on the device in a fixed launch sequence with
     one host copy at the end.  Returns a RescoreResult filled as beam_search fills a BeamResult: tokens (B, nbest,
     1 + L) = BOS, labels, EOS..., lengths = labels + 1 (0: no such hypothesis), scores = the combined score, plus
-    att_scores and ctc_scores.  Eval only: dropout is off."""
+    att_scores and ctc_scores.  Eval only: dropout is off.
+
+    mbr_scale = a number >= 0: the final order is the minimum-Bayes-risk one instead.  The first pass's labels, still
+    on the device, go through asrx_edit_distance (all beam x beam pairs per sample) and asrx_mbr_rank with the
+    posterior softmax(mbr_scale * combined score): two more launches before the same single host copy, and `risks`
+    is filled.  None (default) issues exactly the launches above."""
     lam = float(ctc_weight)
     if lam != lam or lam < 0.0:
         raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
+    if mbr_scale is not None:
+        mbr_scale = float(mbr_scale)
+        if mbr_scale != mbr_scale or mbr_scale < 0.0:
+            raise ValueError(f"mbr_scale {mbr_scale} must be >= 0")
     if ctc is None:
         raise RuntimeError("asrx: rescoring needs the CTC head's logits (a model built with ctc=True)")
     W, nbest = _check_beam(beam, nbest)
@@ -973,7 +984,7 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     if B == 0:
         z = torch.zeros(0, nbest, dtype=torch.float32)
         return RescoreResult(torch.zeros(0, nbest, 1 + L, dtype=torch.int64), torch.zeros(0, nbest, dtype=torch.int64),
-                             z, z.clone(), z.clone())
+                             z, z.clone(), z.clone(), None if mbr_scale is None else z.clone())
     R = B * W
     tok, lens, cscore, n_hyp = _first_pass(ctc, B, cls.V, W, max_labels, dev)
     dec_in, dec_tgt, mask = K.hyp_tokens(tok, lens, n_hyp, B, W, L, BOS_ID, eos, pad, IGNORE_ID)
@@ -982,8 +993,15 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     logits, _ = decoder_fwd(C, dec, dec_in, mask, enc_c, R, L, Te, final_norm=final_norm, group=W)
     att = K.seq_logprob(logits, cls.V, dec_tgt, IGNORE_ID, n_hyp, W)
     score, order = K.rescore_rank(att, cscore, B, W, 1.0, lam)
-    flat = _words(dec_tgt, lens, order, score, att, cscore).cpu()
     f32, i32 = torch.float32, torch.int32
+    if mbr_scale is None:
+        risk = None
+        flat = _words(dec_tgt, lens, order, score, att, cscore).cpu()
+    else:
+        dist, _ = K.edit_distance(tok, None, lens, None, (), None, "cross", W, n_hyp, counts=False)
+        risk, order = K.mbr_rank(dist, score, B, W, mbr_scale, n_hyp)
+        flat = _words(dec_tgt, lens, order, score, att, cscore, risk).cpu()
+        risk = flat[-B * W:].view(f32).reshape(B, W)
     tgt, lens, order, score, att, cscore = _split(flat, ((B, W, L), torch.int64), ((B, W), i32), ((B, W), i32),
                                                   ((B, W), f32), ((B, W), f32), ((B, W), f32))
     order = order[:, :nbest].long()
@@ -992,7 +1010,8 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     rows = torch.where(rows == IGNORE_ID, torch.full_like(rows, eos), rows)
     tokens = torch.cat([torch.full((B, nbest, 1), BOS_ID, dtype=torch.int64), rows], dim=2)
     lengths = torch.where(live, lens.gather(1, order).long() + 1, torch.zeros(B, nbest, dtype=torch.int64))
-    return RescoreResult(tokens, lengths, score.gather(1, order), att.gather(1, order), cscore.gather(1, order))
+    return RescoreResult(tokens, lengths, score.gather(1, order), att.gather(1, order), cscore.gather(1, order),
+                         None if risk is None else risk.gather(1, order))
 
 
 def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbest=1, max_len=None):
@@ -1006,7 +1025,7 @@ def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbe
 
 
 def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True,
-                        max_len=None):
+                        max_len=None, mbr_scale=None):
     """Transformer.rescore: front end and encoder as in `evaluate`, the CTC head on the one encoder output, then
     decoder_rescore."""
     if getattr(model, "ctc_head", None) is None:
@@ -1019,7 +1038,7 @@ def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=N
         enc = model.encoder(model.input_layer(spectrum))
     logits, B, T = _ctc_logits_of(model, enc)
     return decoder_rescore(model.decoder, enc, (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V), beam,
-                           lam, nbest, final_norm, max_len)
+                           lam, nbest, final_norm, max_len, mbr_scale)
 
 
 # ------------------------------------------------------------------------------------------- sub-modules

@@ -1203,6 +1203,70 @@ def rescore_rank(att, ctc, B, W, att_weight, ctc_weight):
     return score, order
 
 
+ED_MODES = {"pairs": 0, "group": 1, "cross": 2}    # ASRX_ED_PAIRS / GROUP / CROSS
+
+
+def _rows(t, name):
+    assert t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] > 0 and t.stride(1) == 1 and \
+        t.stride(0) >= t.shape[1], f"asrx: edit_distance needs int64 {name} rows [n, cols > 0] of unit column stride"
+
+
+def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, drop=(), stop=None, mode="pairs", W=1,
+                  n_hyp=None, counts=True, out=None):
+    """Levenshtein alignment of token rows (asrx_edit_distance).  hyp int64 [R, cols] (any row stride), ref int64
+    [R', cols'] (None in "cross" mode), lengths int32 per row or None (= cols).  A row's sequence: its first `length`
+    entries, cut before the first `stop` id (None: no stop), without the (at most four) `drop` ids.  "pairs": R' = R
+    pairs; "group": row n against ref row n // W; "cross": R // W groups, all W x W pairs of each.  n_hyp int32 per
+    group: slots >= n_hyp[g] are absent (dist -1).  Returns (dist int32 [N], counts int32 [N, 4] = sub, del, ins,
+    reference tokens, or None with counts=False); out = (dist, counts) reuses buffers (a captured graph)."""
+    _cuda(hyp, ref, hyp_lengths, ref_lengths, n_hyp)
+    code = ED_MODES[mode]
+    _rows(hyp, "hyp")
+    R = hyp.shape[0]
+    W = int(W)
+    assert len(drop) <= 4 and W >= 1
+    if mode == "cross":
+        assert R % W == 0
+        N, groups, ref_rows = R * W, R // W, 0
+    else:
+        assert ref is not None, "asrx: edit_distance needs reference rows"
+        _rows(ref, "ref")
+        N, groups = R, R // W
+        ref_rows = R if mode == "pairs" else groups
+        assert ref.shape[0] == ref_rows and (mode == "pairs" or R % W == 0)
+    for a, n in ((hyp_lengths, R), (ref_lengths, ref_rows), (n_hyp, groups)):
+        assert a is None or (a.dtype == torch.int32 and a.numel() == n and a.is_contiguous())
+    dev = hyp.device
+    if out is None:
+        dist = torch.empty(N, dtype=torch.int32, device=dev)
+        cnt = torch.empty(N, 4, dtype=torch.int32, device=dev) if counts else None
+    else:
+        dist, cnt = out
+        assert dist.dtype == torch.int32 and dist.numel() == N and dist.is_contiguous()
+        assert cnt is None or (cnt.dtype == torch.int32 and cnt.numel() == 4 * N and cnt.is_contiguous())
+    ids = (ctypes.c_int64 * 4)(*[int(d) for d in drop])
+    cross = mode == "cross"
+    call("asrx_edit_distance", hyp.data_ptr(), hyp.stride(0), hyp.shape[1], _p(hyp_lengths),
+         None if cross else ref.data_ptr(), 0 if cross else ref.stride(0), 0 if cross else ref.shape[1],
+         None if cross else _p(ref_lengths), N, code, W, None if mode == "pairs" else _p(n_hyp), ids, len(drop),
+         -1 if stop is None else int(stop), dist.data_ptr(), _p(cnt), stream())
+    return dist, cnt
+
+
+def mbr_rank(dist, score, B, W, scale=1.0, n_hyp=None):
+    """Minimum-Bayes-risk ranking (asrx_mbr_rank): dist int32 [B*W*W] pairwise distances, score fp32 [B*W] ->
+    (risk fp32 [B, W] by slot, order int32 [B, W] = slots by ascending risk, dead slots last)."""
+    _cuda(dist, score, n_hyp)
+    assert dist.dtype == torch.int32 and dist.numel() == B * W * W and dist.is_contiguous()
+    assert score.dtype == torch.float32 and score.numel() == B * W and score.is_contiguous()
+    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() == B and n_hyp.is_contiguous())
+    risk = torch.empty(B, W, dtype=torch.float32, device=dist.device)
+    order = torch.empty(B, W, dtype=torch.int32, device=dist.device)
+    call("asrx_mbr_rank", dist.data_ptr(), score.data_ptr(), _p(n_hyp), B, W, float(scale), risk.data_ptr(),
+         order.data_ptr(), stream())
+    return risk, order
+
+
 def adam(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, decoupled=False, hyp=None):
     """Fused Adam/AdamW step `step` (1-based).  hyp (optional fp32 device [3]): lr and bias corrections read by
     the kernel at run time (a replayed HIP graph; see adam_hyper)."""

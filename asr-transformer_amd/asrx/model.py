@@ -205,11 +205,12 @@ class Decoder(nn.Module):
         return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
                                    ctc_weight)
 
-    def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None):
+    def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None):
         """Two-pass decoding from an encoder output and its CTC logits, ctc = (logits, T, blank, input_lengths) as in
-        beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult."""
+        beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult.  mbr_scale: a number
+        orders the hypotheses by minimum Bayes risk under softmax(mbr_scale * score) and fills `risks`."""
         from .functions import decoder_rescore
-        return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len)
+        return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len, mbr_scale)
 
 
 class Transformer(nn.Module):
@@ -291,10 +292,25 @@ class Transformer(nn.Module):
         from .functions import transformer_ctc_beam_search
         return transformer_ctc_beam_search(self, spectrum, beam, input_lengths, nbest)
 
-    def rescore(self, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True, max_len=None):
+    def rescore(self, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True, max_len=None,
+                mbr_scale=None):
         """Two-pass decoding (ctc=True models): ctc_beam_search's `beam` hypotheses, one teacher-forced decoder forward
         over all of them, ranked by log p_att + ctc_weight * log p_ctc.  Returns a RescoreResult: a BeamResult
         filled as beam_search fills it (tokens BOS, labels, EOS...; lengths count the EOS; scores combined) with
-        att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample (the CTC frames only)."""
+        att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample (the CTC frames only).
+        mbr_scale = a number >= 0: the order is the minimum-Bayes-risk one under softmax(mbr_scale * score) over the
+        `beam` hypotheses (asrx_edit_distance + asrx_mbr_rank on the device) and `risks` is filled; None: as before."""
         from .functions import transformer_rescore
-        return transformer_rescore(self, spectrum, beam, ctc_weight, input_lengths, nbest, final_norm, max_len)
+        return transformer_rescore(self, spectrum, beam, ctc_weight, input_lengths, nbest, final_norm, max_len,
+                                   mbr_scale)
+
+    def token_drop_ids(self, bos_token_id=1):
+        """The ids that are no labels: (BOS, EOS, PAD) and the CTC blank where it is another id.  As `drop` they
+        reduce a transcript row, a beam-search row and a CTC row alike to their labels (asrx.ErrorRate,
+        asrx.edit_distance, asrx.mbr_rerank)."""
+        ids = [int(bos_token_id), int(self.decoder._eos_token_id)]
+        if self.decoder.pad_token_id is not None:
+            ids.append(int(self.decoder.pad_token_id))
+        if getattr(self, "ctc_head", None) is not None:
+            ids.append(self.ctc_blank)
+        return tuple(dict.fromkeys(ids))

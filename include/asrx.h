@@ -36,7 +36,8 @@ extern "C" {
  * of beam-search decoding.  5: asrx_ctc_loss, asrx_ctc_workspace_elems, asrx_ctc_targets, asrx_ctc_greedy.
  * 6: joint CTC/attention beam search: asrx_ctc_prefix_init, asrx_ctc_prefix_score, asrx_ctc_prefix_advance,
  * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
- * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words). */
+ * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words.  9: token error rates and
+ * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -617,6 +618,50 @@ int asrx_ctc_align(const float* logits, int32_t B, int32_t T, int32_t V, int64_t
                    int32_t max_target_len, int32_t blank, void* ws, int64_t ws_words, int32_t* frame_pos,
                    float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score,
                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Edit distance and minimum-Bayes-risk ranking (version >= 9): how many errors a decoder's output holds against a
+ * transcript, and which hypothesis of an n-best list has the smallest expected distance to the others.
+ * ------------------------------------------------------------------------------------------------- */
+#define ASRX_ED_PAIRS 0   /* pair n = hyp row n against ref row n */
+#define ASRX_ED_GROUP 1   /* pair n = hyp row n against ref row n / W: B * W hypotheses against B references */
+#define ASRX_ED_CROSS 2   /* N = G * W * W, pair (g, i, j) = hyp row g * W + i against hyp row g * W + j; ref unused */
+/* Levenshtein alignment of N pairs of token rows.  A row is int64 [cols] of row stride ld >= cols with an optional
+ * int32 length (NULL: cols; clamped to [0, cols]); its SEQUENCE is its first `len` entries, cut before the first one
+ * equal to stop_id (stop_id < 0: no stop), without every entry equal to one of drop[0 .. ndrop) (a HOST array,
+ * ndrop <= 4, as in asrx_ctc_targets).  That covers `text` rows (BOS, labels, EOS, PAD...), beam-search rows (prompt,
+ * tokens, EOS fill) and CTC rows (labels, blank fill).  Tokens are only compared, never used as an index.  In CROSS
+ * mode both rows are hyp rows (hyp_cols, ld_hyp, hyp_len) and ref / ld_ref / ref_cols / ref_len are ignored.
+ * n_hyp (GROUP and CROSS; nullable, int32 [N / W] and [N / W^2]): slots j >= n_hyp[g] of group g are absent.
+ * Minimised is the pair (edits, substitutions) lexicographically: among the alignments with the fewest edits one
+ * with the fewest substitutions, i.e. the most exact matches.  That is an optimum, not a backtrace rule, so any
+ * two implementations agree exactly: hyp (a, b) against ref (b, c) is 2 edits = 0 sub + 1 del + 1 ins, not 2 sub.
+ * A deletion is a reference token without a hypothesis counterpart, an insertion a hypothesis token without a
+ * reference counterpart.
+ * Outputs (every element written by every call):
+ *   dist    int32 [N]      edits; -1: the pair involves an absent slot; -2: a sequence of more than 255 tokens
+ *   counts  int32 [N][4]   (sub, del, ins, reference tokens), -1 where dist < 0; nullable
+ * In CROSS mode dist is symmetric with a zero diagonal, and (i, j) and (j, i) have del and ins swapped.
+ * ASRX_ERR_ARG, before any device access, for N <= 0, cols <= 0, ld < cols, ndrop outside 0..4, ndrop > 0 with a NULL
+ * drop, a NULL hyp or dist, a NULL ref in PAIRS or GROUP mode, W < 1 (GROUP) or outside 1..16 (CROSS), N no multiple
+ * of W (GROUP) or W * W (CROSS), an unknown mode.  One wave64 per pair, integer arithmetic only; no host round trip,
+ * no allocation, graph-capturable, deterministic. */
+int asrx_edit_distance(const int64_t* hyp, int64_t ld_hyp, int32_t hyp_cols, const int32_t* hyp_len,
+                       const int64_t* ref, int64_t ld_ref, int32_t ref_cols, const int32_t* ref_len, int32_t N,
+                       int32_t mode, int32_t W, const int32_t* n_hyp, const int64_t* drop, int32_t ndrop,
+                       int64_t stop_id, int32_t* dist, int32_t* counts, void* stream);
+/* Minimum-Bayes-risk ranking of B n-best lists from their pairwise distances (asrx_edit_distance in CROSS mode):
+ * dist int32 [B][W][W], score fp32 [B][W], n_hyp int32 [B] or NULL.  Slot j is live if j < n_hyp[b], its score is
+ * finite and dist[b][j][j] >= 0 (an absent or unsupported hypothesis is dead).  With p_j = exp(scale * (s_j - max live
+ * s)) / (sum over the live slots), risk_i = sum over the live j, ascending, of p_j * dist[b][i][j], in fp32; a dead
+ * slot has risk +inf.  scale = 0 weighs the live slots equally (the medoid).
+ *   risk   fp32  [B][W]
+ *   order  int32 [B][W]   slots by (risk ascending, slot ascending), dead slots last: asrx_rescore_rank's convention
+ * Two slots with identical dist rows get bitwise-equal risks and so stay in slot order.  1 <= W <= 16; ASRX_ERR_ARG,
+ * before any device access, for W outside that, B <= 0, a negative or NaN scale, a NULL dist, score, risk or order.
+ * One wave per sample, one launch; graph-capturable, deterministic. */
+int asrx_mbr_rank(const int32_t* dist, const float* score, const int32_t* n_hyp, int32_t B, int32_t W, float scale,
+                  float* risk, int32_t* order, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
