@@ -7,7 +7,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import MAX_ROWSUM_GROUPS, AttnDesc, BF16, BITS, F32, GemmDesc, RowsumGroup, call
+from ._lib import CTC_MAX_TARGET, MAX_ROWSUM_GROUPS, AttnDesc, BF16, BITS, F32, GemmDesc, RowsumGroup, call
 
 _U64 = (1 << 64) - 1
 
@@ -1013,30 +1013,20 @@ def ctc_loss(logits, V, T, targets, target_lengths, input_lengths=None, max_targ
     loss_scale * reduction, nll fp32 [B], dlogits [B*T, ld] in grad_dtype or None)."""
     _cuda(logits, targets, target_lengths, input_lengths, loss_add)
     rows, ld = logits.shape
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
-        "asrx: ctc_loss needs contiguous fp32 logits [B*T, ld]"
-    assert T > 0 and rows % T == 0
-    B = rows // T
-    assert targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[0] == B
-    assert targets.shape[1] == 0 or targets.stride(1) == 1
-    if max_target_len is None:
-        max_target_len = targets.shape[1]
-    assert max_target_len <= targets.shape[1]
-    for a in (target_lengths, input_lengths):
-        assert a is None or (a.dtype == torch.int32 and a.numel() == B and a.is_contiguous())
+    B = _ctc_logits(logits, T, input_lengths, "ctc_loss")
+    max_target_len, tgt_stride, tgt_ptr = _ctc_targets(targets, target_lengths, B, max_target_len)
     assert loss_add is None or (loss_add.dtype == torch.float32 and loss_add.numel() == 1)
     dev = logits.device
     loss = torch.empty(1, device=dev, dtype=torch.float32)
     nll = torch.empty(B, device=dev, dtype=torch.float32)
     dl = torch.empty(rows, ld, device=dev, dtype=grad_dtype) if want_grad else None
     # (the size rule refuses what the call refuses: let the call report a too long target)
-    n = ctc_workspace_elems(B, T, min(max(max_target_len, 0), 255))
+    n = ctc_workspace_elems(B, T, min(max(max_target_len, 0), CTC_MAX_TARGET))
     ws = torch.empty(n, device=dev, dtype=torch.float32)
-    tgt_stride = targets.stride(0) if targets.shape[1] else 0
-    call("asrx_ctc_loss", logits.data_ptr(), B, T, V, ld, targets.data_ptr() if targets.numel() else None, tgt_stride,
-         _p(input_lengths), target_lengths.data_ptr(), max_target_len, blank, CTC_REDUCTIONS[reduction],
-         int(zero_infinity), grad_scale, nll.data_ptr(), loss.data_ptr(), _p(dl), code(dl) if dl is not None else 0,
-         _p(loss_add), loss_add_scale, loss_scale, ws.data_ptr(), n, stream())
+    call("asrx_ctc_loss", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride, _p(input_lengths),
+         target_lengths.data_ptr(), max_target_len, blank, CTC_REDUCTIONS[reduction], int(zero_infinity), grad_scale,
+         nll.data_ptr(), loss.data_ptr(), _p(dl), code(dl) if dl is not None else 0, _p(loss_add),
+         loss_add_scale, loss_scale, ws.data_ptr(), n, stream())
     return loss, nll, dl
 
 
@@ -1050,8 +1040,7 @@ def ctc_targets(text, mask, drop, blank):
     B, n = text.shape
     targets = torch.empty(B, n, dtype=torch.int64, device=text.device)
     lengths = torch.empty(B, dtype=torch.int32, device=text.device)
-    ids = (ctypes.c_int64 * 4)(*[int(d) for d in drop])
-    call("asrx_ctc_targets", text.data_ptr(), text.stride(0), mask.data_ptr(), mask.stride(0), B, n, ids, len(drop),
+    call("asrx_ctc_targets", text.data_ptr(), text.stride(0), mask.data_ptr(), mask.stride(0), B, n, *_drop_ids(drop),
          int(blank), targets.data_ptr(), n, lengths.data_ptr(), stream())
     return targets, lengths
 
@@ -1060,12 +1049,8 @@ def ctc_greedy(logits, V, T, blank, input_lengths=None):
     """CTC best path of logits fp32 [B*T, ld] (asrx_ctc_greedy): (tokens int64 [B, T] left-packed, padded with
     `blank`; lengths int32 [B]).  Frames t >= input_lengths[b] (int32 [B], None = T) are ignored."""
     _cuda(logits, input_lengths)
-    rows, ld = logits.shape
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld
-    assert T > 0 and rows % T == 0
-    B = rows // T
-    assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == B
-                                     and input_lengths.is_contiguous())
+    ld = logits.shape[1]
+    B = _ctc_logits(logits, T, input_lengths)
     tok = torch.empty(B, T, dtype=torch.int64, device=logits.device)
     lens = torch.empty(B, dtype=torch.int32, device=logits.device)
     call("asrx_ctc_greedy", logits.data_ptr(), B, T, V, ld, _p(input_lengths), blank, tok.data_ptr(), lens.data_ptr(),
@@ -1078,12 +1063,8 @@ def ctc_prefix_beam(logits, V, T, blank, W, max_labels, input_lengths=None):
     (tok int64 [B*W, max_labels] padded with `blank`, len int32 [B*W], score fp32 [B*W] (dead slots: -inf),
     n_hyp int32 [B])."""
     _cuda(logits, input_lengths)
-    rows, ld = logits.shape
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld
-    assert T > 0 and rows % T == 0
-    B = rows // T
-    assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == B
-                                     and input_lengths.is_contiguous())
+    ld = logits.shape[1]
+    B = _ctc_logits(logits, T, input_lengths)
     dev = logits.device
     words = B * T * (6 * W + 1)      # the header's workspace rule
     ws = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
@@ -1128,22 +1109,13 @@ def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_tar
     T) are ignored.  max_target_len is the host-side bound of the lengths (default: the targets' width, at most 255).
     Returns a CtcAlignment; nothing leaves the device."""
     _cuda(logits, targets, target_lengths, input_lengths)
-    rows, ld = logits.shape
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
-        "asrx: ctc_align needs contiguous fp32 logits [B*T, ld]"
-    assert T > 0 and rows % T == 0
-    B = rows // T
-    assert targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[0] == B
-    assert targets.shape[1] == 0 or targets.stride(1) == 1
-    if max_target_len is None:
-        max_target_len = targets.shape[1]
-    assert max_target_len <= targets.shape[1]
-    for a in (target_lengths, input_lengths):
-        assert a is None or (a.dtype == torch.int32 and a.numel() == B and a.is_contiguous())
+    ld = logits.shape[1]
+    B = _ctc_logits(logits, T, input_lengths, "ctc_align")
+    max_target_len, tgt_stride, tgt_ptr = _ctc_targets(targets, target_lengths, B, max_target_len)
     dev = logits.device
     lmax = max(max_target_len, 0)
     # (the size rule refuses what the call refuses: let the call report a too long target)
-    words = ctc_align_workspace_words(B, T, min(lmax, 255))
+    words = ctc_align_workspace_words(B, T, min(lmax, CTC_MAX_TARGET))
     ws = torch.empty(words, dtype=torch.int32, device=dev)
     frame_pos = torch.empty(B, T, dtype=torch.int32, device=dev)
     frame_logp = torch.empty(B, T, dtype=torch.float32, device=dev)
@@ -1151,11 +1123,10 @@ def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_tar
     end = torch.empty(B, lmax, dtype=torch.int32, device=dev)
     conf = torch.empty(B, lmax, dtype=torch.float32, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
-    tgt_stride = targets.stride(0) if targets.shape[1] else 0
-    call("asrx_ctc_align", logits.data_ptr(), B, T, V, ld, targets.data_ptr() if targets.numel() else None, tgt_stride,
-         _p(input_lengths), target_lengths.data_ptr(), max_target_len, blank, ws.data_ptr(), words,
-         frame_pos.data_ptr(), frame_logp.data_ptr(), start.data_ptr() if lmax else None,
-         end.data_ptr() if lmax else None, conf.data_ptr() if lmax else None, score.data_ptr(), stream())
+    call("asrx_ctc_align", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride, _p(input_lengths),
+         target_lengths.data_ptr(), max_target_len, blank, ws.data_ptr(), words, frame_pos.data_ptr(),
+         frame_logp.data_ptr(), start.data_ptr() if lmax else None, end.data_ptr() if lmax else None,
+         conf.data_ptr() if lmax else None, score.data_ptr(), stream())
     return CtcAlignment(frame_pos, frame_logp, start, end, conf, score, targets, target_lengths)
 
 
@@ -1166,7 +1137,7 @@ def hyp_tokens(tok, lens, n_hyp, B, W, L, bos, eos, pad, ignore):
     R = B * W
     assert tok.dtype == torch.int64 and tok.dim() == 2 and tok.shape[0] == R and tok.stride(1) == 1
     assert lens.dtype == torch.int32 and lens.numel() == R and lens.is_contiguous()
-    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() == B and n_hyp.is_contiguous())
+    _check_n_hyp(n_hyp, B)
     dev = tok.device
     dec_in = torch.empty(R, L, dtype=torch.int64, device=dev)
     dec_tgt = torch.empty(R, L, dtype=torch.int64, device=dev)
@@ -1183,7 +1154,7 @@ def seq_logprob(logits, V, tgt, ignore, n_hyp=None, W=1):
     N, L = tgt.shape
     assert logits.dtype == torch.float32 and logits.shape[0] == N * L and logits.stride(1) == 1
     assert logits.shape[1] >= V and tgt.dtype == torch.int64 and tgt.is_contiguous()
-    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() * W == N and n_hyp.is_contiguous())
+    _check_n_hyp(n_hyp, N, W)
     out = torch.empty(N, dtype=torch.float32, device=logits.device)
     call("asrx_seq_logprob", logits.data_ptr(), N, L, V, logits.stride(0), tgt.data_ptr(), int(ignore), _p(n_hyp),
          int(W), out.data_ptr(), stream())
@@ -1204,6 +1175,35 @@ def rescore_rank(att, ctc, B, W, att_weight, ctc_weight):
 
 
 ED_MODES = {"pairs": 0, "group": 1, "cross": 2}    # ASRX_ED_PAIRS / GROUP / CROSS
+
+
+def _ctc_logits(logits, T, input_lengths, who=None):   # -> B of logits fp32 [B*T, ld], input_lengths int32 [B] or None
+    rows, ld = logits.shape
+    if not (logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld):
+        raise AssertionError(*([f"asrx: {who} needs contiguous fp32 logits [B*T, ld]"] if who else []))
+    assert T > 0 and rows % T == 0
+    assert input_lengths is None or (input_lengths.dtype == torch.int32 and input_lengths.numel() == rows // T
+                                     and input_lengths.is_contiguous())
+    return rows // T
+
+
+def _ctc_targets(targets, target_lengths, B, max_target_len):   # -> (max_target_len, tgt_stride, targets pointer)
+    assert targets.dtype == torch.int64 and targets.dim() == 2 and targets.shape[0] == B
+    assert targets.shape[1] == 0 or targets.stride(1) == 1
+    max_target_len = targets.shape[1] if max_target_len is None else max_target_len
+    assert max_target_len <= targets.shape[1]
+    assert target_lengths is None or (target_lengths.dtype == torch.int32 and target_lengths.numel() == B
+                                      and target_lengths.is_contiguous())
+    tgt_stride = targets.stride(0) if targets.shape[1] else 0   # (no columns: stride 0 and a null pointer)
+    return max_target_len, tgt_stride, targets.data_ptr() if targets.numel() else None
+
+
+def _check_n_hyp(n_hyp, rows, W=1):   # None, or one int32 count per group of W of the rows
+    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() * W == rows and n_hyp.is_contiguous())
+
+
+def _drop_ids(drop):   # (ids, count): the at most four drop ids as the C-ABI takes them
+    return (ctypes.c_int64 * 4)(*[int(d) for d in drop]), len(drop)
 
 
 def _rows(t, name):
@@ -1234,8 +1234,9 @@ def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, drop=(), st
         N, groups = R, R // W
         ref_rows = R if mode == "pairs" else groups
         assert ref.shape[0] == ref_rows and (mode == "pairs" or R % W == 0)
-    for a, n in ((hyp_lengths, R), (ref_lengths, ref_rows), (n_hyp, groups)):
+    for a, n in ((hyp_lengths, R), (ref_lengths, ref_rows)):
         assert a is None or (a.dtype == torch.int32 and a.numel() == n and a.is_contiguous())
+    _check_n_hyp(n_hyp, groups)
     dev = hyp.device
     if out is None:
         dist = torch.empty(N, dtype=torch.int32, device=dev)
@@ -1244,11 +1245,10 @@ def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, drop=(), st
         dist, cnt = out
         assert dist.dtype == torch.int32 and dist.numel() == N and dist.is_contiguous()
         assert cnt is None or (cnt.dtype == torch.int32 and cnt.numel() == 4 * N and cnt.is_contiguous())
-    ids = (ctypes.c_int64 * 4)(*[int(d) for d in drop])
     cross = mode == "cross"
     call("asrx_edit_distance", hyp.data_ptr(), hyp.stride(0), hyp.shape[1], _p(hyp_lengths),
          None if cross else ref.data_ptr(), 0 if cross else ref.stride(0), 0 if cross else ref.shape[1],
-         None if cross else _p(ref_lengths), N, code, W, None if mode == "pairs" else _p(n_hyp), ids, len(drop),
+         None if cross else _p(ref_lengths), N, code, W, None if mode == "pairs" else _p(n_hyp), *_drop_ids(drop),
          -1 if stop is None else int(stop), dist.data_ptr(), _p(cnt), stream())
     return dist, cnt
 
@@ -1259,7 +1259,7 @@ def mbr_rank(dist, score, B, W, scale=1.0, n_hyp=None):
     _cuda(dist, score, n_hyp)
     assert dist.dtype == torch.int32 and dist.numel() == B * W * W and dist.is_contiguous()
     assert score.dtype == torch.float32 and score.numel() == B * W and score.is_contiguous()
-    assert n_hyp is None or (n_hyp.dtype == torch.int32 and n_hyp.numel() == B and n_hyp.is_contiguous())
+    _check_n_hyp(n_hyp, B)
     risk = torch.empty(B, W, dtype=torch.float32, device=dist.device)
     order = torch.empty(B, W, dtype=torch.int32, device=dist.device)
     call("asrx_mbr_rank", dist.data_ptr(), score.data_ptr(), _p(n_hyp), B, W, float(scale), risk.data_ptr(),

@@ -181,6 +181,43 @@ ASRX_DEV float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// wave-wide maximum on wave_sum's DPP / permlane ladder (every step joins a lane and its partner: all lanes agree).
+// Precondition: all 64 lanes are active at the call (an inactive partner contributes 0, not -inf).
+ASRX_DEV float wave_max_dpp(float v) {
+  v = fmaxf(v, dpp_f<0xB1>(v));
+  v = fmaxf(v, dpp_f<0x4E>(v));
+  v = fmaxf(v, dpp_f<0x141>(v));
+  v = fmaxf(v, dpp_f<0x140>(v));
+  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+  r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+
+// lane i <- lane i - 1 (lane 0 <- fill) and lane i <- lane i + 1 (lane 63 <- fill): DPP wave_shr:1 / wave_shl:1
+ASRX_DEV int wave_up1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xF, 0xF, false); }
+ASRX_DEV int wave_down1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xF, 0xF, false); }
+ASRX_DEV float wave_up1(float v, float fill) {
+  return __int_as_float(wave_up1(__float_as_int(v), __float_as_int(fill)));
+}
+ASRX_DEV float wave_down1(float v, float fill) {
+  return __int_as_float(wave_down1(__float_as_int(v), __float_as_int(fill)));
+}
+
+// what this wave wrote to LDS is read by its other lanes after this (wave scope: no workgroup barrier)
+ASRX_DEV void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// a length read from the device, clamped to [0, hi]
+ASRX_DEV int clamp_len(int n, int hi) { return n < 0 ? 0 : (n > hi ? hi : n); }
+
+// The beam order (asrx_beam_step's, shared by every selection): score descending, index ascending, a total order
+// once NaN scores are read as -inf (nonan).  ranks_before: a ranks before b.
+ASRX_DEV float nonan(float x) { return x != x ? -INFINITY : x; }
+ASRX_DEV bool ranks_before(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 
 #define ASRX_CHECK_LAUNCH()                         \
   do {                                              \

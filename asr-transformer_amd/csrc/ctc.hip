@@ -20,40 +20,14 @@
 //                         dlogits = gs * (softmax - occupancy).
 //   4. ctc_finish_kernel  loss = loss_add_scale * loss_add[0] + loss_scale * sum_b w_b nll_b, fixed order.
 // No floating-point atomics anywhere: two calls on the same inputs give the same bits.
-#include "common.h"
+#include "ctc_common.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
-constexpr int CTC_MAXL = 255;        // L + 1 <= 256 pairs = 64 lanes x 4
 constexpr int CTC_AUX = 260;         // ints per sample: [0, 256) rank | count << 16, [256] L (-1: no alignment can
                                      // exist: bad length or label), [257] input length
-
-ASRX_DEV float log2_raw(float x) { return __builtin_amdgcn_logf(x); }
-
-// log2(2^a + 2^b) and log2(2^a + 2^b + 2^c); -inf operands (and all -inf) are legal
-ASRX_DEV float lae2(float a, float b) {
-  const float hi = fmaxf(a, b), lo = fminf(a, b);
-  const float hs = hi == -INFINITY ? 0.f : hi;
-  return hi + log2_raw(1.f + exp2_raw(lo - hs));
-}
-ASRX_DEV float lae3(float a, float b, float c) {
-  const float hi = fmaxf(fmaxf(a, b), c), lo = fminf(fminf(a, b), c);
-  const float mid = __builtin_amdgcn_fmed3f(a, b, c);
-  const float hs = hi == -INFINITY ? 0.f : hi;
-  return hi + log2_raw(1.f + exp2_raw(mid - hs) + exp2_raw(lo - hs));
-}
-
-// lane i <- lane i - 1 (lane 0 <- fill) and lane i <- lane i + 1 (lane 63 <- fill): DPP wave_shr:1 / wave_shl:1
-ASRX_DEV float wave_up1(float v, float fill) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x138, 0xF, 0xF, false));
-}
-ASRX_DEV float wave_down1(float v, float fill) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(v), 0x130, 0xF, 0xF, false));
-}
 
 struct CtcWs {
   float* stats;   // [B*T][2]: row max, log2 sum
@@ -63,7 +37,6 @@ struct CtcWs {
   float* beta;
 };
 
-inline int ctc_kp(int max_l) { return (max_l + 1 + 63) / 64; }
 inline int64_t r4(int64_t x) { return (x + 3) & ~(int64_t)3; }
 inline int64_t ctc_ws_elems(int64_t B, int64_t T, int max_l) {
   return r4(2 * B * T) + r4(B * CTC_AUX) + r4(B) + 2 * B * T * 128 * ctc_kp(max_l);
@@ -113,7 +86,7 @@ __global__ __launch_bounds__(256) void ctc_prep_kernel(const float* __restrict__
     aux[b * CTC_AUX + tid] = word;
     if (tid == 0) {
       int Tb = input_lengths ? input_lengths[b] : T;
-      Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+      Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);   // (written out: clamp_len moves one instruction of this kernel)
       aux[b * CTC_AUX + 256] = (len_ok && !bad) ? L : -1;
       aux[b * CTC_AUX + 257] = Tb;
     }
@@ -430,8 +403,7 @@ __global__ __launch_bounds__(1024) void ctc_greedy_kernel(const float* __restric
                                                           int64_t* __restrict__ tok, int32_t* __restrict__ len) {
   extern __shared__ int s_am[];   // [T] per-frame arg-max
   const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int Tb = input_lengths ? input_lengths[b] : T;
-  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  const int Tb = clamp_len(input_lengths ? input_lengths[b] : T, T);
   for (int t = wv; t < Tb; t += 16) {
     const float* x = logits + ((int64_t)b * T + t) * ld;
     float mx = -INFINITY;
@@ -481,15 +453,14 @@ extern "C" int asrx_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t 
                              float grad_scale, float* nll, float* loss, void* dlogits, int32_t dlogits_dtype,
                              const float* loss_add, float loss_add_scale, float loss_scale, float* ws,
                              int64_t ws_elems, void* stream) {
-  if (B <= 0 || T <= 0 || V <= 0 || ld < V || max_target_len < 0 || tgt_stride < 0) return ASRX_ERR_ARG;
-  if (blank < 0 || blank >= V) return ASRX_ERR_ARG;
+  // (these two stand before the first ASRX_ERR_UNSUPPORTED of the shared checks, whose earlier ones return
+  // ASRX_ERR_ARG as well: a call that breaks several rules gets the same code wherever among those they stand)
   if (reduction != ASRX_CTC_SUM && reduction != ASRX_CTC_MEAN) return ASRX_ERR_ARG;
   if (dlogits && dlogits_dtype != ASRX_BF16 && dlogits_dtype != ASRX_F32) return ASRX_ERR_ARG;
-  if (max_target_len > CTC_MAXL) return ASRX_ERR_UNSUPPORTED;
-  if (tgt_stride < max_target_len) return ASRX_ERR_ARG;
-  if (!logits || !target_lengths || !nll || !loss || !ws || (max_target_len > 0 && !targets)) return ASRX_ERR_ARG;
-  if (((uintptr_t)ws & 15) != 0 || ws_elems < ctc_ws_elems(B, T, max_target_len)) return ASRX_ERR_ARG;
-  if ((int64_t)B * T > 0x7fffffffLL / 4 || B > 65535) return ASRX_ERR_UNSUPPORTED;
+  const bool own_ok = logits && target_lengths && nll && loss && ws && ((uintptr_t)ws & 15) == 0 &&
+                      ws_elems >= ctc_ws_elems(B, T, std::min(max_target_len, CTC_MAXL));   // (beyond: refused before)
+  const int err = ctc_check_target_args(B, T, V, ld, targets, tgt_stride, max_target_len, blank, own_ok);
+  if (err != ASRX_OK) return err;
   if (ld > 8192) return ASRX_ERR_UNSUPPORTED;   // the gradient's per-wave occupancy row lives in LDS
   hipStream_t st = (hipStream_t)stream;
   const CtcWs w = ctc_ws(ws, B, T, max_target_len);
@@ -497,19 +468,16 @@ extern "C" int asrx_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t 
   const int64_t rows = (int64_t)B * T;
   const int mean = reduction == ASRX_CTC_MEAN;
   const int vec_in = ld % 4 == 0 && ((uintptr_t)logits & 15) == 0;
-  static const int64_t no_targets[1] = {0};
-  const int64_t* tg = targets ? targets : no_targets;   // (never read: every length is clamped to max_target_len = 0)
+  const int64_t* tg = ctc_targets_or_dummy(targets);
 
   hipLaunchKernelGGL(ctc_prep_kernel, dim3((unsigned)(B + (rows + 3) / 4)), dim3(256), 0, st, logits, B, T, V, ld, tg,
                      tgt_stride, input_lengths, target_lengths, max_target_len, blank, vec_in, w.stats, w.aux);
   ASRX_CHECK_LAUNCH();
   const dim3 cgrid((unsigned)B, 2);
-  switch (kp) {
-    case 1: hipLaunchKernelGGL(ctc_chain_kernel<1>, cgrid, dim3(64), 0, st, logits, T, ld, tg, tgt_stride, blank, w, nll); break;
-    case 2: hipLaunchKernelGGL(ctc_chain_kernel<2>, cgrid, dim3(64), 0, st, logits, T, ld, tg, tgt_stride, blank, w, nll); break;
-    case 3: hipLaunchKernelGGL(ctc_chain_kernel<3>, cgrid, dim3(64), 0, st, logits, T, ld, tg, tgt_stride, blank, w, nll); break;
-    default: hipLaunchKernelGGL(ctc_chain_kernel<4>, cgrid, dim3(64), 0, st, logits, T, ld, tg, tgt_stride, blank, w, nll); break;
-  }
+  ctc_dispatch_kp(kp, [&](auto kpc) {
+    hipLaunchKernelGGL(ctc_chain_kernel<decltype(kpc)::value>, cgrid, dim3(64), 0, st, logits, T, ld, tg, tgt_stride,
+                       blank, w, nll);
+  });
   ASRX_CHECK_LAUNCH();
   if (dlogits) {
     const int ldp = (int)((ld + 3) & ~(int64_t)3);

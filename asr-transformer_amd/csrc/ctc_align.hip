@@ -23,33 +23,15 @@
 // The backpointers live in LDS while T <= 1008 (128 B per frame, with the 2 KiB of run boundaries exactly 128 KiB);
 // a longer T keeps them in the workspace instead (asrx_ctc_align_workspace_words grows accordingly).
 // No atomics, fixed orders: the same inputs give the same bits.  Every output element is written by every call.
-#include "common.h"
+#include "ctc_common.h"
 
 namespace {
 
-constexpr int AL_MAXL = 255;          // L + 1 <= 256 pairs = 64 lanes x 4
 constexpr int AL_U = 4;               // frames of emissions in flight (8 measured the same)
 constexpr int AL_LDS_T = 1008;        // longest T whose backpointers stay in LDS: 1008 * 128 B + 2 KiB = 128 KiB
 constexpr int AL_STATIC_LDS = 2048;   // s_start + s_end
 
-inline int al_kp(int max_l) { return (max_l + 1 + 63) / 64; }
 inline int64_t al_ws_words(int64_t B, int64_t T) { return 2 * B * T + (T > AL_LDS_T ? 32 * B * T : 0); }
-
-// lane i <- lane i - 1 (lane 0 <- fill): DPP wave_shr:1
-ASRX_DEV int al_up1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xF, 0xF, false); }
-ASRX_DEV float al_up1(float v, float fill) { return __int_as_float(al_up1(__float_as_int(v), __float_as_int(fill))); }
-
-// wave-wide maximum on wave_sum's DPP / permlane ladder (every step joins a lane and its partner: all lanes agree)
-ASRX_DEV float al_wave_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-  r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
 
 // ---------------------------------------------------------------------------------------------- 1. row logsumexp
 __global__ __launch_bounds__(256) void align_rows_kernel(const float* __restrict__ logits, int64_t rows, int V,
@@ -83,8 +65,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
   int L = target_lengths[b];
   const bool len_ok = L >= 0 && L <= max_l;
   if (!len_ok) L = 0;
-  int Tb = input_lengths ? input_lengths[b] : T;
-  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  const int Tb = clamp_len(input_lengths ? input_lengths[b] : T, T);
   const int64_t* tg = targets + (int64_t)b * tgt_stride;
   const int64_t row0 = (int64_t)b * T;
   const float* lse = lse_all + row0;
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
     bad |= bd;
     lab[q] = (vl[q] && !bd) ? (int)id : blank;
   }
-  const int in_lab = al_up1(lab[KP - 1], -1);
+  const int in_lab = wave_up1(lab[KP - 1], -1);
 #pragma unroll
   for (int q = 0; q < KP; ++q) {
     const int u = lane * KP + q;
@@ -155,7 +136,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
       float m = -INFINITY;
 #pragma unroll
       for (int q = 0; q < KP; ++q) m = fmaxf(m, fmaxf(sb[q], sl[q]));
-      m = al_wave_max(m);
+      m = wave_max_dpp(m);
       if (!(m > -INFINITY) || m == INFINITY) m = 0.f;
       off += (double)m;
 #pragma unroll
@@ -167,7 +148,7 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
       for (int i = 0; i < AL_U; ++i) {
         if (k0 + i >= Tb) break;
         const float eb = c_b[i] - c_s[i];
-        const float in_l = al_up1(sl[KP - 1], -INFINITY);   // label state of pair u - 1 for q = 0
+        const float in_l = wave_up1(sl[KP - 1], -INFINITY);   // label state of pair u - 1 for q = 0
         float nb[KP], nl[KP];
         unsigned word = 0;
 #pragma unroll
@@ -277,25 +258,10 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
   if (lane == 0) score[b] = sc;
 }
 
-template <int KP>
-void al_launch(bool spill, int B, size_t shm, hipStream_t st, const float* logits, int T, int V, int64_t ld,
-               const int64_t* tg, int64_t tgt_stride, const int32_t* input_lengths, const int32_t* target_lengths,
-               int max_l, int blank, const float* lse, int32_t* path, uint16_t* bp, int32_t* frame_pos,
-               float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score) {
-  if (spill)
-    hipLaunchKernelGGL((ctc_align_kernel<KP, true>), dim3((unsigned)B), dim3(64), 0, st, logits, T, V, ld, tg,
-                       tgt_stride, input_lengths, target_lengths, max_l, blank, lse, path, bp, frame_pos, frame_logp,
-                       tok_start, tok_end, tok_conf, score);
-  else
-    hipLaunchKernelGGL((ctc_align_kernel<KP, false>), dim3((unsigned)B), dim3(64), shm, st, logits, T, V, ld, tg,
-                       tgt_stride, input_lengths, target_lengths, max_l, blank, lse, path, bp, frame_pos, frame_logp,
-                       tok_start, tok_end, tok_conf, score);
-}
-
 }  // namespace
 
 extern "C" int64_t asrx_ctc_align_workspace_words(int32_t B, int32_t T, int32_t max_target_len) {
-  if (B <= 0 || T <= 0 || max_target_len < 0 || max_target_len > AL_MAXL) return -1;
+  if (B <= 0 || T <= 0 || max_target_len < 0 || max_target_len > CTC_MAXL) return -1;
   return al_ws_words(B, T);
 }
 
@@ -304,14 +270,11 @@ extern "C" int asrx_ctc_align(const float* logits, int32_t B, int32_t T, int32_t
                               int32_t max_target_len, int32_t blank, void* ws, int64_t ws_words, int32_t* frame_pos,
                               float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score,
                               void* stream) {
-  if (B <= 0 || T <= 0 || V <= 0 || ld < V || max_target_len < 0 || tgt_stride < 0) return ASRX_ERR_ARG;
-  if (blank < 0 || blank >= V) return ASRX_ERR_ARG;
-  if (max_target_len > AL_MAXL) return ASRX_ERR_UNSUPPORTED;
-  if (tgt_stride < max_target_len) return ASRX_ERR_ARG;
-  if (!logits || !target_lengths || !ws || !frame_pos || !frame_logp || !score) return ASRX_ERR_ARG;
-  if (max_target_len > 0 && (!targets || !tok_start || !tok_end || !tok_conf)) return ASRX_ERR_ARG;
-  if (((uintptr_t)ws & 3) != 0 || ws_words < al_ws_words(B, T)) return ASRX_ERR_ARG;
-  if ((int64_t)B * T > 0x7fffffffLL / 4 || B > 65535) return ASRX_ERR_UNSUPPORTED;
+  const bool own_ok = logits && target_lengths && ws && frame_pos && frame_logp && score &&
+                      (max_target_len <= 0 || (tok_start && tok_end && tok_conf)) && ((uintptr_t)ws & 3) == 0 &&
+                      ws_words >= al_ws_words(B, T);
+  const int err = ctc_check_target_args(B, T, V, ld, targets, tgt_stride, max_target_len, blank, own_ok);
+  if (err != ASRX_OK) return err;
   const bool spill = T > AL_LDS_T;
   const size_t shm = spill ? 0 : (size_t)T * 128;
   if (shm + AL_STATIC_LDS > 128 * 1024) return ASRX_ERR_UNSUPPORTED;   // (cannot happen: AL_LDS_T is that bound)
@@ -320,18 +283,18 @@ extern "C" int asrx_ctc_align(const float* logits, int32_t B, int32_t T, int32_t
   float* lse = (float*)ws;
   int32_t* path = (int32_t*)ws + rows;
   uint16_t* bp = (uint16_t*)((int32_t*)ws + 2 * rows);   // (spill only: the workspace ends here otherwise)
-  static const int64_t no_targets[1] = {0};
-  const int64_t* tg = targets ? targets : no_targets;   // (never read: every length is clamped to max_target_len = 0)
+  const int64_t* tg = ctc_targets_or_dummy(targets);
 
   hipLaunchKernelGGL(align_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, logits, rows, (int)V, ld,
                      lse);
   ASRX_CHECK_LAUNCH();
-  switch (al_kp(max_target_len)) {
-    case 1: al_launch<1>(spill, B, shm, st, logits, T, V, ld, tg, tgt_stride, input_lengths, target_lengths, max_target_len, blank, lse, path, bp, frame_pos, frame_logp, tok_start, tok_end, tok_conf, score); break;
-    case 2: al_launch<2>(spill, B, shm, st, logits, T, V, ld, tg, tgt_stride, input_lengths, target_lengths, max_target_len, blank, lse, path, bp, frame_pos, frame_logp, tok_start, tok_end, tok_conf, score); break;
-    case 3: al_launch<3>(spill, B, shm, st, logits, T, V, ld, tg, tgt_stride, input_lengths, target_lengths, max_target_len, blank, lse, path, bp, frame_pos, frame_logp, tok_start, tok_end, tok_conf, score); break;
-    default: al_launch<4>(spill, B, shm, st, logits, T, V, ld, tg, tgt_stride, input_lengths, target_lengths, max_target_len, blank, lse, path, bp, frame_pos, frame_logp, tok_start, tok_end, tok_conf, score); break;
-  }
+  ctc_dispatch_kp(ctc_kp(max_target_len), [&](auto kpc) {
+    constexpr int KP = decltype(kpc)::value;
+    const auto kernel = spill ? ctc_align_kernel<KP, true> : ctc_align_kernel<KP, false>;   // (spill: shm = 0)
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), shm, st, logits, (int)T, (int)V, ld, tg, tgt_stride,
+                       input_lengths, target_lengths, (int)max_target_len, (int)blank, (const float*)lse, path, bp,
+                       frame_pos, frame_logp, tok_start, tok_end, tok_conf, score);
+  });
   ASRX_CHECK_LAUNCH();
   return ASRX_OK;
 }

@@ -38,7 +38,7 @@
 // max-subtracted, no atomics, fixed orders: the same inputs give the same bits.
 #include <limits.h>
 
-#include "common.h"
+#include "ctc_common.h"
 
 namespace {
 
@@ -49,15 +49,12 @@ constexpr int CB_MAXC = 136;   // sum over w < 16 of ceil(32 / (w + 1)) = 114 ex
 constexpr int CB_XR = 8;       // most logits of a row a lane keeps in registers (V <= 512)
 constexpr int CB_MAXV = 1 << 20;
 
-ASRX_DEV float cb_nonan(float x) { return x != x ? -INFINITY : x; }
-// a ranks before b (asrx_beam_step's order)
-ASRX_DEV bool cb_before(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 // log(e^a + e^b), max-subtracted, on the raw v_exp_f32 / v_log_f32 (absolute error ~1e-7: the argument of the
 // logarithm lies in [1, 2]); -inf operands are legal
 ASRX_DEV float cb_lae(float a, float b) {
   const float hi = fmaxf(a, b), lo = fminf(a, b);
   if (!(hi > -INFINITY)) return -INFINITY;
-  return hi + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + exp2_raw((lo - hi) * 1.4426950408889634f));
+  return hi + kLn2 * log2_raw(1.f + exp2_raw((lo - hi) * kLog2e));
 }
 
 // A candidate as one 64-bit key: a ranks before b exactly when key(a) > key(b).  High word: the score's bits made
@@ -119,8 +116,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_prefix_beam_kernel(
   constexpr int XRC = REG ? XR : 1;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = 2 * W;
-  int Tb = input_lengths ? input_lengths[b] : T;
-  Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
+  const int Tb = clamp_len(input_lengths ? input_lengths[b] : T, T);
   const float* x0 = logits + (int64_t)b * T * ld;
   float* w_lse = ws + (int64_t)b * cb_ws_words(T, W);
   float* w_topx = w_lse + T;
@@ -162,13 +158,11 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_prefix_beam_kernel(
 #pragma unroll
       for (int j = 0; j < XRC; ++j) {
         const int c = lane + 64 * j;
-        key[j] = c < V && c != blank ? cb_key(cb_nonan(xv[j]), c) : 0;
+        key[j] = c < V && c != blank ? cb_key(nonan(xv[j]), c) : 0;
         row[c] = key[j];
         r[j] = 0;
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the other lanes' keys, written above, are read below
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();   // the other lanes' keys, written above, are read below
       const cb_key2_t* row2 = (const cb_key2_t*)row;
       const int pairs = (V + 63) / 64 * 32;   // whole 64-column groups: the tail holds zeros
 #pragma unroll 4
@@ -196,14 +190,14 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_prefix_beam_kernel(
         int bi = INT_MAX;
         for (int c = lane; c < V; c += 64) {
           if (c == blank) continue;
-          const float v = cb_nonan(x[c]);
-          if (cb_before(ps, pi, v, c) && cb_before(v, c, bs, bi)) { bs = v; bi = c; }
+          const float v = nonan(x[c]);
+          if (ranks_before(ps, pi, v, c) && ranks_before(v, c, bs, bi)) { bs = v; bi = c; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
           const float os = __shfl_xor(bs, o, 64);
           const int oi = __shfl_xor(bi, o, 64);
-          if (cb_before(os, oi, bs, bi)) { bs = os; bi = oi; }
+          if (ranks_before(os, oi, bs, bi)) { bs = os; bi = oi; }
         }
         if (lane == 0) {
           w_topx[(int64_t)t * K + k] = bs;
@@ -278,8 +272,8 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_prefix_beam_kernel(
         for (int j = 0; j < n; ++j) w0 = s_h[j] == ph ? j : w0;
         if (w0 >= 0) pnb = cb_lae(pnb, (last == s_last[w0] ? s_pb[w0] : s_tot[w0]) + yl);
       }
-      pb = cb_nonan(pb);
-      pnb = cb_nonan(pnb);
+      pb = nonan(pb);
+      pnb = nonan(pnb);
       s_spb[w] = pb;
       s_spnb[w] = pnb;
       s_c[next + w] = cb_key(cb_lae(pb, pnb), w * V + blank);
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(CB_THREADS) void ctc_prefix_beam_kernel(
         const uint64_t h = s_h[w];
         bool merged = false;
         for (int w1 = 0; w1 < n; ++w1) merged |= s_ph[w1] == h && s_last[w1] == c;
-        if (!merged && s_len[w] < max_labels) sc = cb_nonan((c == s_last[w] ? s_pb[w] : s_tot[w]) + (s_tx[k] - lse));
+        if (!merged && s_len[w] < max_labels) sc = nonan((c == s_last[w] ? s_pb[w] : s_tot[w]) + (s_tx[k] - lse));
       }
       s_c[lt] = cb_key(sc, idx);
       s_cw[lt] = w;
@@ -423,7 +417,7 @@ __global__ __launch_bounds__(64) void hyp_tokens_kernel(const int64_t* __restric
   const int r = blockIdx.x, lane = threadIdx.x;
   const bool dead = n_hyp && (r % W) >= n_hyp[r / W];
   int n = len[r];
-  n = n < 0 ? 0 : (n > L - 1 ? L - 1 : n);
+  n = clamp_len(n, L - 1);
   n = n > ld_tok ? (int)ld_tok : n;
   const int64_t* src = tok + (int64_t)r * ld_tok;
   for (int i = lane; i < L; i += 64) {
@@ -476,12 +470,12 @@ __global__ __launch_bounds__(64) void rescore_rank_kernel(const float* __restric
   if (lane < W) {
     const float a = att[b * W + lane], c = ctc[b * W + lane];
     // a dead hypothesis (either term -inf) stays dead under a zero weight
-    if (a > -INFINITY && c > -INFINITY) s = cb_nonan(__builtin_fmaf(ctc_w, c, att_w * a));
+    if (a > -INFINITY && c > -INFINITY) s = nonan(__builtin_fmaf(ctc_w, c, att_w * a));
   }
   int r = 0;
   for (int j = 0; j < W; ++j) {
     const float o = __shfl(s, j, 64);
-    r += cb_before(o, j, s, lane) ? 1 : 0;
+    r += ranks_before(o, j, s, lane) ? 1 : 0;
   }
   if (lane < W) {
     score[b * W + lane] = s;

@@ -15,23 +15,12 @@
 //
 // Everything is fp32 in the log2 domain (v_exp_f32 / v_log_f32), every log-sum-exp max-subtracted; the scores leave
 // in natural-log units.  No atomics, fixed summation orders: the same inputs give the same bits.
-#include "common.h"
+#include "ctc_common.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 constexpr int PFX_MAXW = 16;
 constexpr int PFX_SLICES = 4;   // waves of a scoring workgroup: each sweeps a quarter of the frames
-
-ASRX_DEV float log2_raw(float x) { return __builtin_amdgcn_logf(x); }
-
-// log2(2^a + 2^b); -inf operands (and both -inf) are legal
-ASRX_DEV float lae2(float a, float b) {
-  const float hi = fmaxf(a, b), lo = fminf(a, b);
-  const float hs = hi == -INFINITY ? 0.f : hi;
-  return hi + log2_raw(1.f + exp2_raw(lo - hs));
-}
 
 // running (max, sum of 2^(x - max)) of a log-sum-exp: one exponential per term
 ASRX_DEV void lse_push(float& m, float& s, float x) {
@@ -47,8 +36,6 @@ ASRX_DEV void lse_merge(float& m, float& s, float m2, float s2) {
   s = s * exp2_raw(m - hs) + s2 * exp2_raw(m2 - hs);
   m = hi;
 }
-
-ASRX_DEV int clamp_frames(int n, int T) { return n < 0 ? 0 : (n > T ? T : n); }
 
 // ---------------------------------------------------------------------------------------------- init
 // one wave per (b, t) row: logp[r][c] = log2 softmax(logits[r])[c]
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(64) void prefix_root_kernel(const float* __restrict
                                                          int32_t* __restrict__ frames, float* __restrict__ state,
                                                          float* __restrict__ logpsi, int32_t* __restrict__ last) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int Tb = clamp_frames(input_lengths ? input_lengths[b] : T, T);
+  const int Tb = clamp_len(input_lengths ? input_lengths[b] : T, T);
   if (lane == 0) frames[b] = Tb;
   if (lane < W) {
     logpsi[b * W + lane] = 0.f;
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(64 * PFX_SLICES) void prefix_score_kernel(
   const int b = blockIdx.y;
   const int c = blockIdx.x * 64 + lane;
   const int cc = c < V ? c : V - 1;   // lanes past V read column V - 1 and store nothing
-  const int Tb = clamp_frames(frames[b], T);
+  const int Tb = clamp_len(frames[b], T);
   const int per = (Tb + PFX_SLICES - 1) / PFX_SLICES;
   const int t0 = slice * per;
   const int t1 = t0 + per < Tb ? t0 + per : Tb;
@@ -207,7 +194,7 @@ __global__ __launch_bounds__(64) void prefix_advance_kernel(
   const int slot = blockIdx.x, lane = threadIdx.x;
   const int b = slot / W;
   int p = parent[slot];
-  p = p < 0 ? 0 : (p >= W ? W - 1 : p);
+  p = clamp_len(p, W - 1);
   const int64_t ps = (int64_t)b * W + p;
   const int64_t tk = tok[slot];
   const int c = tk < 0 ? 0 : (tk >= V ? V - 1 : (int)tk);
@@ -221,7 +208,7 @@ __global__ __launch_bounds__(64) void prefix_advance_kernel(
     }
     return;
   }
-  const int Tb = clamp_frames(frames[b], T);
+  const int Tb = clamp_len(frames[b], T);
   const int lst = last_in[ps];
   const bool same = c == lst;
   const float phi0 = lst < 0 ? 0.f : -INFINITY;

@@ -23,20 +23,13 @@ struct BeamBest {
   float s;
   int i;
 };
-// a ranks before b
-ASRX_DEV bool beam_before(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
-
-ASRX_DEV float beam_cand(float score, float logit, float lse) {
-  const float c = score + (logit - lse);
-  return c != c ? -INFINITY : c;
-}
+ASRX_DEV float beam_cand(float score, float logit, float lse) { return nonan(score + (logit - lse)); }
 
 // the joint candidate: score + att_w * (logit - lse) + ext_w * extra.  The multiply-adds are explicit so that the LDS
 // and the re-read path round alike whatever the compiler would contract; att_w = 1, ext_w = 0 with extra = 0 is
 // beam_cand bit for bit.
 ASRX_DEV float beam_cand_joint(float score, float logit, float lse, float att_w, float ext_w, float extra) {
-  const float c = __builtin_fmaf(ext_w, extra, __builtin_fmaf(att_w, logit - lse, score));
-  return c != c ? -INFINITY : c;
+  return nonan(__builtin_fmaf(ext_w, extra, __builtin_fmaf(att_w, logit - lse, score)));
 }
 
 struct BeamExtra {
@@ -100,7 +93,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
       float c;
       if (s_fin[w]) {
         const float s = s_score[w];
-        c = v == eos ? (s != s ? -INFINITY : s) : __builtin_nanf("");
+        c = v == eos ? nonan(s) : __builtin_nanf("");
       } else {
         c = JOINT ? beam_cand_joint(s_score[w], x0[(int64_t)w * ld + v], s_lse[w], ex.att_w, ex.ext_w,
                                     e0[(int64_t)w * ex.ld + v])
@@ -120,16 +113,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
     if (LDS) {
       for (int i = tid; i < n; i += BEAM_THREADS) {
         const float c = cand[i];
-        if (c == c && beam_before(ps, pi, c, i) && beam_before(c, i, bs, bi)) { bs = c; bi = i; }
+        if (c == c && ranks_before(ps, pi, c, i) && ranks_before(c, i, bs, bi)) { bs = c; bi = i; }
       }
     } else {
       for (int w = 0; w < W; ++w) {
         const float sc = s_score[w];
         if (s_fin[w]) {
           if (tid == 0) {
-            const float c = sc != sc ? -INFINITY : sc;
+            const float c = nonan(sc);
             const int i = w * V + eos;
-            if (beam_before(ps, pi, c, i) && beam_before(c, i, bs, bi)) { bs = c; bi = i; }
+            if (ranks_before(ps, pi, c, i) && ranks_before(c, i, bs, bi)) { bs = c; bi = i; }
           }
           continue;
         }
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
         for (int v = tid; v < V; v += BEAM_THREADS) {
           const float c = JOINT ? beam_cand_joint(sc, x[v], lse, ex.att_w, ex.ext_w, e[v]) : beam_cand(sc, x[v], lse);
           const int i = w * V + v;
-          if (beam_before(ps, pi, c, i) && beam_before(c, i, bs, bi)) { bs = c; bi = i; }
+          if (ranks_before(ps, pi, c, i) && ranks_before(c, i, bs, bi)) { bs = c; bi = i; }
         }
       }
     }
@@ -147,7 +140,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
     for (int o = 32; o > 0; o >>= 1) {
       const float os = __shfl_xor(bs, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (beam_before(os, oi, bs, bi)) { bs = os; bi = oi; }
+      if (ranks_before(os, oi, bs, bi)) { bs = os; bi = oi; }
     }
     const int pp = j & 1;   // two exchange slots: round j+1 writes the other one, so one barrier per round
     if (lane == 0) {
@@ -161,7 +154,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_step_kernel(
     for (int k = 1; k < BEAM_WAVES; ++k) {
       const float os = s_rs[pp][k];
       const int oi = s_ri[pp][k];
-      if (beam_before(os, oi, bs, bi)) { bs = os; bi = oi; }
+      if (ranks_before(os, oi, bs, bi)) { bs = os; bi = oi; }
     }
     // every sample has at least W candidates (V per live beam, one per finished beam), so bi is a real index
     ps = bs;

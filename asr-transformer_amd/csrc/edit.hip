@@ -38,18 +38,6 @@ struct EdFilter {
   int ndrop;
 };
 
-// lane i <- lane i - 1 (lane 0 <- fill): DPP wave_shr:1
-ASRX_DEV int ed_up1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xF, 0xF, false); }
-
-ASRX_DEV int ed_clamp(int x, int hi) { return x < 0 ? 0 : (x > hi ? hi : x); }
-
-// what this wave wrote to LDS is read by its other lanes below
-ASRX_DEV void ed_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the sequence of row[0 .. len) -> s[0 .. min(count, 256)); returns the count (> ED_MAXL: too long, s is incomplete)
 ASRX_DEV int ed_load(const int64_t* __restrict__ row, int len, const EdFilter& f, int64_t* s, int lane) {
   int cnt = 0;
@@ -113,7 +101,7 @@ __global__ __launch_bounds__(64 * ED_WAVES) void edit_distance_kernel(
     int lh = hyp_len ? hyp_len[hr] : hyp_cols;
     lh = lh < 0 ? 0 : (lh > hyp_cols ? hyp_cols : lh);
     int lr = rlen ? rlen[rr] : rcols;
-    lr = lr < 0 ? 0 : (lr > rcols ? rcols : lr);
+    lr = lr < 0 ? 0 : (lr > rcols ? rcols : lr);   // (both written out: through clamp_len this kernel's code moves)
     m = ed_load(hyp + hr * ld_hyp, lh, f, sh, lane);
     nn = ed_load(rbase + rr * rld, lr, f, sr, lane);
     if (m > ED_MAXL || nn > ED_MAXL) code = -2;
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(64 * ED_WAVES) void edit_distance_kernel(
   int packed = ED_EDIT * (m + nn);   // one side empty: all insertions or all deletions
   if (m > 0 && nn > 0) {
     for (int i = lane; i <= m; i += 64) bd[i] = ED_EDIT * i;   // column 0: i insertions
-    ed_wave_sync();
+    wave_lds_sync();
     const int nblk = (nn + 63) >> 6;
     int v = 0;
     for (int blk = 0; blk < nblk; ++blk) {
@@ -141,9 +129,9 @@ __global__ __launch_bounds__(64 * ED_WAVES) void edit_distance_kernel(
       for (int s = 0; s < steps; ++s) {
         const int i = s - lane;   // this lane's row (of the hypothesis, 0-based) at this step
         const bool act = (unsigned)i < (unsigned)m;
-        const int64_t ht_n = sh[ed_clamp(i + 1, m - 1)];   // the next step's operands, read while this one computes
+        const int64_t ht_n = sh[clamp_len(i + 1, m - 1)];   // the next step's operands, read while this one computes
         const int fill_n = bd[s + 2 < m ? s + 2 : m];
-        const int left = ed_up1(v, fill);
+        const int left = wave_up1(v, fill);
         const int dg = lp + (ht == rt ? 0 : ED_EDIT + 1);
         int nv = (v < left ? v : left) + ED_EDIT;
         nv = nv < dg ? nv : dg;
@@ -153,7 +141,7 @@ __global__ __launch_bounds__(64 * ED_WAVES) void edit_distance_kernel(
         ht = ht_n;
         fill = fill_n;
       }
-      ed_wave_sync();
+      wave_lds_sync();
     }
     packed = __shfl(v, (nn - 1) & 63, 64);
   }
