@@ -175,11 +175,19 @@ SIGNATURES = {
     "asrx_edit_distance": [c_vp, c_i64, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32,
                            c_i64, c_vp, c_vp, c_vp],
     "asrx_mbr_rank": [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp],
+    # (the n-gram table leads: first_child, token, logp, backoff, n_nodes, order, V)
+    "asrx_ngram_score": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_i64, c_f32, c_f32, c_f32,
+                         c_vp, c_i64, c_vp],
+    "asrx_ngram_advance": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp,
+                           c_vp, c_vp],
+    "asrx_ngram_seq_logprob": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_i32, c_i64, c_i32,
+                               c_vp, c_i32, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
 ED_PAIRS, ED_GROUP, ED_CROSS = 0, 1, 2    # asrx_edit_distance pairing modes
 CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended states)
+NGRAM_MAX_ORDER = 6         # ASRX_NGRAM_MAX_ORDER
 
 ERRORS = {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}
 

@@ -4,6 +4,7 @@ flat gradient buffer that `p.grad` views (asrx.params); the Functions return Non
 
 `model_forward` / `model_backward` are also used directly (no autograd) by the fused trainer (asrx.train).
 """
+import math
 import os
 from typing import NamedTuple
 
@@ -663,9 +664,26 @@ def beam_rank(scores, lengths, length_penalty):
     return torch.sort(key, dim=1, descending=True, stable=True).indices
 
 
+def check_lm(lm, lm_weight, token_bonus, V=None):
+    """The LM arguments of the decoders, checked before any device work: (lm_weight, token_bonus) as floats, the weight
+    0.0 where no LM takes part (lm=None or lm_weight == 0: the decoders then issue exactly the launches they issue
+    without these arguments, and token_bonus is not applied).  V: the classifier's vocabulary, which the LM's must
+    equal."""
+    beta, bonus = float(lm_weight), float(token_bonus)
+    if beta != beta or beta < 0.0 or math.isinf(beta):
+        raise ValueError(f"lm_weight {lm_weight} must be a finite number >= 0")
+    if not math.isfinite(bonus):
+        raise ValueError(f"token_bonus {token_bonus} must be finite")
+    if lm is None or beta == 0.0:
+        return 0.0, 0.0
+    if V is not None and lm.vocab_size != V:
+        raise ValueError(f"the LM's vocabulary ({lm.vocab_size}) is not the classifier's ({V})")
+    return beta, bonus
+
+
 @torch.no_grad()
 def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
-                        ctc=None, ctc_weight=0.0):
+                        ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0):
     """Beam-search decoding on the KV-cached decoder (the reference has none: Decoder.evaluate, model.py:125-151, is
     greedy).  x (B, L0 >= 1) is the prompt, prefilled with teacher forcing; `max_len` new tokens (default seq_len)
     are then chosen with `beam` hypotheses per sample, each step keeping the `beam` best continuations by summed
@@ -686,10 +704,20 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
     the utterances, their frame count, the blank id and optional int32 frame counts per sample.  Every selecting step
     then scores the whole vocabulary (asrx_ctc_prefix_score), selects (asrx_beam_step_joint) and advances the
     survivors' CTC states (asrx_ctc_prefix_advance), all on the device.  The prompt must be one token (the CTC
-    prefix is the generated labels only).  ctc_weight = 0 (default) is the attention-only search, launch for launch."""
+    prefix is the generated labels only).  ctc_weight = 0 (default) is the attention-only search, launch for launch.
+
+    lm (an asrx.NgramLM on the device) with lm_weight = beta > 0 adds shallow fusion: every generated token, the EOS
+    included, also earns beta * log p_lm(token | BOS, the tokens before it) + token_bonus, so a finished hypothesis
+    scores (1 - lam) * log p_att + lam * log p_ctc + beta * log p_lm + token_bonus * len.  Two more launches per step:
+    asrx_ngram_score writes the `extra` matrix of asrx_beam_step_joint (with lam > 0 it folds lam * the CTC scores in),
+    asrx_ngram_advance moves the survivors' LM contexts.  The prompt must be one token, the LM's sentence start.
+    lm=None or lm_weight = 0 (default) issues exactly the launches described above."""
     lam = float(ctc_weight)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1]")
+    beta, bonus = check_lm(lm, lm_weight, token_bonus, dec._classifier.V)
+    if beta > 0.0 and x.dim() == 2 and x.shape[1] != 1:
+        raise ValueError(f"lm_weight > 0 takes a one-token prompt, got L0 = {x.shape[1]}")
     if lam > 0.0:
         if ctc is None:
             raise RuntimeError("asrx: ctc_weight > 0 needs the CTC head's logits (a model built with ctc=True)")
@@ -750,6 +778,10 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
             ctc_lengths = ctc_lengths.to(device=dev, dtype=torch.int32).contiguous()
         prefix = K.CtcPrefix(ctc_logits, B, W, int(ctc_T), V, ctc_blank, ctc_lengths)
         delta = torch.empty(R, Vp, dtype=torch.float32, device=dev)
+    ngram = None
+    if beta > 0.0:
+        ngram = K.NgramState(lm, B, W)
+        extra = torch.empty(R, Vp, dtype=torch.float32, device=dev)
     for t in range(P):
         xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te)
         s = t - (L0 - 1)
@@ -763,13 +795,24 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
             K.cast(xs, hc)
         lg = torch.empty(R, Vp, dtype=torch.float32, device=dev)
         K.gemm(hc, C.W(cls.weight), lg, R, Vp, d, lda=d, ldb=d, ldc=Vp)
-        if prefix is None:
+        if prefix is None and ngram is None:
             K.beam_step(lg, V, B, W, eos, state, other, tok_h[s], par_h[s], src_row, cur=cur, n_live=n_live[s:s + 1])
-        else:
+        elif ngram is None:
             prefix.score(eos, delta)
             K.beam_step_joint(lg, V, B, W, eos, delta, 1.0 - lam, lam, state, other, tok_h[s], par_h[s], src_row,
                               cur=cur, n_live=n_live[s:s + 1])
             prefix.advance(eos, par_h[s], tok_h[s], state[1])
+        else:       # extra = lam * ctc + beta * lm + bonus in one launch, selected with extra_weight = 1
+            if prefix is not None:
+                prefix.score(eos, delta)
+                ngram.score(extra, delta, lam, beta, bonus)
+            else:
+                ngram.score(extra, None, 0.0, beta, bonus)
+            K.beam_step_joint(lg, V, B, W, eos, extra, 1.0 - lam, 1.0, state, other, tok_h[s], par_h[s], src_row,
+                              cur=cur, n_live=n_live[s:s + 1])
+            if prefix is not None:
+                prefix.advance(eos, par_h[s], tok_h[s], state[1])
+            ngram.advance(eos, par_h[s], tok_h[s], state[1])
         state, other = other, state
         if poll and (s + 1) % poll == 0 and s + 1 < steps and int(n_live[s]) == 0:
             done = s + 1
@@ -797,6 +840,9 @@ def transformer_beam_search(model, spectrum, text=None, ctc_weight=0.0, input_le
         raise RuntimeError("asrx: ctc_weight > 0 needs a model with a CTC head (Transformer(..., ctc=True))")
     if lam > 0.0 and text is not None and text.dim() == 2 and text.shape[1] != 1:
         raise ValueError(f"ctc_weight > 0 takes a one-token prompt, got L0 = {text.shape[1]}")
+    beta, _ = check_lm(kw.get("lm"), kw.get("lm_weight", 0.0), kw.get("token_bonus", 0.0), model.decoder._classifier.V)
+    if beta > 0.0 and text is not None and text.dim() == 2 and text.shape[1] != 1:
+        raise ValueError(f"lm_weight > 0 takes a one-token prompt, got L0 = {text.shape[1]}")
     with torch.no_grad():
         enc = model.encoder(model.input_layer(spectrum))
     if text is None:
@@ -870,11 +916,12 @@ class RescoreResult(BeamResult):
     """A BeamResult (tokens, lengths, scores: the same three fields, so it unpacks and indexes alike) that also
     carries the two terms of the combined score: att_scores and ctc_scores, fp32 (B, nbest), and, where the order is
     a minimum-Bayes-risk one (rescore(mbr_scale=...), asrx.mbr_rerank), `risks`: each hypothesis's expected edit
-    distance under the n-best posterior, fp32 (B, nbest), else None."""
+    distance under the n-best posterior, fp32 (B, nbest), else None.  `lm_scores`: each hypothesis's log p_lm where a
+    language model took part in the ranking (rescore(lm=...)), fp32 (B, nbest), else None; ctc_scores stays pure."""
 
-    def __new__(cls, tokens, lengths, scores, att_scores=None, ctc_scores=None, risks=None):
+    def __new__(cls, tokens, lengths, scores, att_scores=None, ctc_scores=None, risks=None, lm_scores=None):
         self = super().__new__(cls, tokens, lengths, scores)
-        self.att_scores, self.ctc_scores, self.risks = att_scores, ctc_scores, risks
+        self.att_scores, self.ctc_scores, self.risks, self.lm_scores = att_scores, ctc_scores, risks, lm_scores
         return self
 
 
@@ -949,7 +996,8 @@ def decoder_ctc_beam_search(dec, ctc, B, beam=8, nbest=1, max_len=None):
 
 
 @torch.no_grad()
-def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None):
+def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None,
+                    lm=None, lm_weight=0.0, token_bonus=0.0):
     """Two-pass decoding ("attention rescoring"): asrx_ctc_prefix_beam yields `beam` complete hypotheses per sample
     from the CTC head's logits alone; ONE teacher-forced decoder forward over all B * beam of them (rows BOS, labels;
     targets labels, EOS; cross-attention grouped per sample, nothing expanded) gives each log p_att, and they are
@@ -962,10 +1010,16 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     mbr_scale = a number >= 0: the final order is the minimum-Bayes-risk one instead.  The first pass's labels, still
     on the device, go through asrx_edit_distance (all beam x beam pairs per sample) and asrx_mbr_rank with the
     posterior softmax(mbr_scale * combined score): two more launches before the same single host copy, and `risks`
-    is filled.  None (default) issues exactly the launches above."""
+    is filled.  None (default) issues exactly the launches above.
+
+    lm (an asrx.NgramLM on the device) with lm_weight = beta > 0: the rank is log p_att + ctc_weight * log p_ctc +
+    beta * log p_lm + token_bonus * len, the LM over the labels and the EOS after its sentence start.  One more launch
+    (asrx_ngram_seq_logprob, which folds the CTC term in; asrx_rescore_rank then adds the two sums), and `lm_scores`
+    is filled.  lm=None or lm_weight = 0 (default) issues exactly the launches above."""
     lam = float(ctc_weight)
     if lam != lam or lam < 0.0:
         raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
+    beta, bonus = check_lm(lm, lm_weight, token_bonus, dec._classifier.V)
     if mbr_scale is not None:
         mbr_scale = float(mbr_scale)
         if mbr_scale != mbr_scale or mbr_scale < 0.0:
@@ -984,7 +1038,8 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     if B == 0:
         z = torch.zeros(0, nbest, dtype=torch.float32)
         return RescoreResult(torch.zeros(0, nbest, 1 + L, dtype=torch.int64), torch.zeros(0, nbest, dtype=torch.int64),
-                             z, z.clone(), z.clone(), None if mbr_scale is None else z.clone())
+                             z, z.clone(), z.clone(), None if mbr_scale is None else z.clone(),
+                             z.clone() if beta > 0.0 else None)
     R = B * W
     tok, lens, cscore, n_hyp = _first_pass(ctc, B, cls.V, W, max_labels, dev)
     dec_in, dec_tgt, mask = K.hyp_tokens(tok, lens, n_hyp, B, W, L, BOS_ID, eos, pad, IGNORE_ID)
@@ -992,16 +1047,23 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     K.cast(enc_x.reshape(B * Te, d).contiguous(), enc_c)
     logits, _ = decoder_fwd(C, dec, dec_in, mask, enc_c, R, L, Te, final_norm=final_norm, group=W)
     att = K.seq_logprob(logits, cls.V, dec_tgt, IGNORE_ID, n_hyp, W)
-    score, order = K.rescore_rank(att, cscore, B, W, 1.0, lam)
-    f32, i32 = torch.float32, torch.int32
-    if mbr_scale is None:
-        risk = None
-        flat = _words(dec_tgt, lens, order, score, att, cscore).cpu()
+    if beta > 0.0:
+        lm_s, rest = K.ngram_seq_logprob(lm, dec_tgt, IGNORE_ID, n_hyp, W, cscore, lam, beta, bonus)
+        score, order = K.rescore_rank(att, rest, B, W, 1.0, 1.0)
     else:
+        score, order = K.rescore_rank(att, cscore, B, W, 1.0, lam)
+    f32, i32 = torch.float32, torch.int32
+    tail = []                                   # optional [B, W] fp32 vectors behind the six fixed ones
+    if mbr_scale is not None:
         dist, _ = K.edit_distance(tok, None, lens, None, (), None, "cross", W, n_hyp, counts=False)
         risk, order = K.mbr_rank(dist, score, B, W, mbr_scale, n_hyp)
-        flat = _words(dec_tgt, lens, order, score, att, cscore, risk).cpu()
-        risk = flat[-B * W:].view(f32).reshape(B, W)
+        tail.append(risk)
+    if beta > 0.0:
+        tail.append(lm_s)
+    flat = _words(dec_tgt, lens, order, score, att, cscore, *tail).cpu()
+    tail = list(flat[flat.numel() - len(tail) * B * W:].view(f32).reshape(len(tail), B, W))
+    lm_s = tail.pop() if beta > 0.0 else None
+    risk = tail.pop() if mbr_scale is not None else None
     tgt, lens, order, score, att, cscore = _split(flat, ((B, W, L), torch.int64), ((B, W), i32), ((B, W), i32),
                                                   ((B, W), f32), ((B, W), f32), ((B, W), f32))
     order = order[:, :nbest].long()
@@ -1011,7 +1073,8 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     tokens = torch.cat([torch.full((B, nbest, 1), BOS_ID, dtype=torch.int64), rows], dim=2)
     lengths = torch.where(live, lens.gather(1, order).long() + 1, torch.zeros(B, nbest, dtype=torch.int64))
     return RescoreResult(tokens, lengths, score.gather(1, order), att.gather(1, order), cscore.gather(1, order),
-                         None if risk is None else risk.gather(1, order))
+                         None if risk is None else risk.gather(1, order),
+                         None if lm_s is None else lm_s.gather(1, order))
 
 
 def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbest=1, max_len=None):
@@ -1025,7 +1088,7 @@ def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbe
 
 
 def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True,
-                        max_len=None, mbr_scale=None):
+                        max_len=None, mbr_scale=None, lm=None, lm_weight=0.0, token_bonus=0.0):
     """Transformer.rescore: front end and encoder as in `evaluate`, the CTC head on the one encoder output, then
     decoder_rescore."""
     if getattr(model, "ctc_head", None) is None:
@@ -1034,11 +1097,12 @@ def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=N
     if lam != lam or lam < 0.0:
         raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
     _check_beam(beam, nbest)
+    check_lm(lm, lm_weight, token_bonus, model.decoder._classifier.V)
     with torch.no_grad():
         enc = model.encoder(model.input_layer(spectrum))
     logits, B, T = _ctc_logits_of(model, enc)
     return decoder_rescore(model.decoder, enc, (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V), beam,
-                           lam, nbest, final_norm, max_len, mbr_scale)
+                           lam, nbest, final_norm, max_len, mbr_scale, lm, lm_weight, token_bonus)
 
 
 # ------------------------------------------------------------------------------------------- sub-modules

@@ -814,6 +814,69 @@ class CtcPrefix:
         self.cur, self.alt = self.alt, self.cur
 
 
+NGRAM_LDS_V = 8192   # ASRX_NGRAM_LDS_V: asrx_ngram_score builds rows of up to this many columns in LDS
+
+
+def _ngram_table(lm, *ts):
+    _cuda(lm.first_child, lm.token, lm.logp, lm.backoff, *ts)
+    return lm.table_args()
+
+
+class NgramState:
+    """The n-gram LM context of B samples x W beams (asrx_ngram_score / asrx_ngram_advance): two sets of ctx int32
+    [B*W, order - 1] that ping-pong as CtcPrefix's do; `cur` holds the hypotheses' contexts, `advance` writes the
+    other one and swaps.  Every slot starts on the LM's sentence-start token.  lm: an asrx.NgramLM on the device."""
+
+    def __init__(self, lm, B, W):
+        self.table = _ngram_table(lm)
+        self.lm, self.B, self.W, self.V = lm, B, W, lm.vocab_size
+        dev = lm.device
+        cols = max(lm.order - 1, 1)           # (a unigram model has no state: one unused column keeps a pointer)
+        root = torch.full((cols,), -1, dtype=torch.int32)
+        if lm.bos_id is not None and lm.order > 1:
+            root[0] = 1 + lm.bos_id
+        self.cur = root.to(dev).repeat(B * W, 1).contiguous()
+        self.alt = torch.empty_like(self.cur)
+
+    def score(self, out, base=None, base_weight=0.0, lm_weight=1.0, bonus=0.0):
+        """out fp32 [B*W, ld >= V] <- base_weight * base + lm_weight * log p_lm(v | slot) + bonus in columns < V
+        (base fp32 [B*W, ld >= V] or None)."""
+        _cuda(out, base)
+        R = self.B * self.W
+        for a in (out, base):
+            assert a is None or (a.dtype == torch.float32 and a.dim() == 2 and a.shape[0] == R and a.stride(1) == 1
+                                 and a.shape[1] >= self.V)
+        call("asrx_ngram_score", *self.table, self.cur.data_ptr(), R, _p(base), base.stride(0) if base is not None
+             else 0, float(base_weight), float(lm_weight), float(bonus), out.data_ptr(), out.stride(0), stream())
+
+    def advance(self, eos, parent, tok, fin_prev):
+        """The chosen slots' contexts from their parents' (the arguments of CtcPrefix.advance)."""
+        _cuda(parent, tok, fin_prev)
+        R = self.B * self.W
+        for a, dt in ((parent, torch.int32), (tok, torch.int64), (fin_prev, torch.uint8)):
+            assert a.dtype == dt and a.numel() == R and a.is_contiguous()
+        call("asrx_ngram_advance", *self.table, self.B, self.W, int(eos), parent.data_ptr(), tok.data_ptr(),
+             fin_prev.data_ptr(), self.cur.data_ptr(), self.alt.data_ptr(), stream())
+        self.cur, self.alt = self.alt, self.cur
+
+
+def ngram_seq_logprob(lm, tgt, ignore, n_hyp=None, W=1, add=None, add_scale=0.0, lm_weight=1.0, bonus=0.0):
+    """Whole-sequence LM scores (asrx_ngram_seq_logprob): tgt int64 [N, L] as for seq_logprob -> (lm fp32 [N] = the
+    summed log p_lm of the scored positions after the LM's sentence start, out fp32 [N] = add_scale * add +
+    lm_weight * lm + bonus * (scored positions)); dead slots (n_hyp, W) give -inf in both."""
+    table = _ngram_table(lm, tgt, n_hyp, add)
+    N, L = tgt.shape
+    assert tgt.dtype == torch.int64 and tgt.stride(1) == 1 and tgt.stride(0) >= L
+    assert add is None or (add.dtype == torch.float32 and add.numel() == N and add.is_contiguous())
+    _check_n_hyp(n_hyp, N, W)
+    lm_out = torch.empty(N, dtype=torch.float32, device=tgt.device)
+    out = torch.empty(N, dtype=torch.float32, device=tgt.device)
+    call("asrx_ngram_seq_logprob", *table, tgt.data_ptr(), tgt.stride(0), N, L, int(ignore),
+         -1 if lm.bos_id is None else lm.bos_id, _p(n_hyp), int(W), _p(add), float(add_scale), float(lm_weight),
+         float(bonus), lm_out.data_ptr(), out.data_ptr(), stream())
+    return lm_out, out
+
+
 def gather_rows(src, dst, index, outer, rows, count, row_stride, outer_stride):
     """dst[o][r][:count] = src[o][index[r]][:count] (asrx_gather_rows) over two buffers of one layout (bf16 or
     fp32, strides in elements); index int32 [rows] holds row numbers in [0, rows)."""

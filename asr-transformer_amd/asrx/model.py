@@ -199,18 +199,23 @@ class Decoder(nn.Module):
         return decoder_evaluate(self, x, enc_x)
 
     def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
-                    ctc=None, ctc_weight=0.0):
-        """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult."""
+                    ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0):
+        """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult.
+        lm / lm_weight / token_bonus: shallow fusion with an asrx.NgramLM on the device."""
         from .functions import decoder_beam_search
         return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
-                                   ctc_weight)
+                                   ctc_weight, lm, lm_weight, token_bonus)
 
-    def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None):
+    def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None,
+                lm=None, lm_weight=0.0, token_bonus=0.0):
         """Two-pass decoding from an encoder output and its CTC logits, ctc = (logits, T, blank, input_lengths) as in
         beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult.  mbr_scale: a number
-        orders the hypotheses by minimum Bayes risk under softmax(mbr_scale * score) and fills `risks`."""
+        orders the hypotheses by minimum Bayes risk under softmax(mbr_scale * score) and fills `risks`.  lm (an
+        asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank and
+        fills `lm_scores`."""
         from .functions import decoder_rescore
-        return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len, mbr_scale)
+        return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len, mbr_scale, lm,
+                               lm_weight, token_bonus)
 
 
 class Transformer(nn.Module):
@@ -254,7 +259,9 @@ class Transformer(nn.Module):
     def beam_search(self, spectrum, text=None, ctc_weight=0.0, input_lengths=None, **kw):
         """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1).
         ctc_weight in (0, 1] (ctc=True models): joint CTC/attention decoding, hypotheses ranked by
-        (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc; input_lengths: valid encoder frames per sample."""
+        (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc; input_lengths: valid encoder frames per sample.
+        lm=, lm_weight=, token_bonus= (an asrx.NgramLM on the device): shallow fusion, every generated token also
+        earns lm_weight * log p_lm + token_bonus; lm=None or lm_weight=0 is the search without an LM."""
         from .functions import transformer_beam_search
         return transformer_beam_search(self, spectrum, text, ctc_weight, input_lengths, **kw)
 
@@ -293,16 +300,18 @@ class Transformer(nn.Module):
         return transformer_ctc_beam_search(self, spectrum, beam, input_lengths, nbest)
 
     def rescore(self, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True, max_len=None,
-                mbr_scale=None):
+                mbr_scale=None, lm=None, lm_weight=0.0, token_bonus=0.0):
         """Two-pass decoding (ctc=True models): ctc_beam_search's `beam` hypotheses, one teacher-forced decoder forward
         over all of them, ranked by log p_att + ctc_weight * log p_ctc.  Returns a RescoreResult: a BeamResult
         filled as beam_search fills it (tokens BOS, labels, EOS...; lengths count the EOS; scores combined) with
         att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample (the CTC frames only).
         mbr_scale = a number >= 0: the order is the minimum-Bayes-risk one under softmax(mbr_scale * score) over the
-        `beam` hypotheses (asrx_edit_distance + asrx_mbr_rank on the device) and `risks` is filled; None: as before."""
+        `beam` hypotheses (asrx_edit_distance + asrx_mbr_rank on the device) and `risks` is filled; None: as before.
+        lm (an asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank
+        (asrx_ngram_seq_logprob) and fills `lm_scores`."""
         from .functions import transformer_rescore
         return transformer_rescore(self, spectrum, beam, ctc_weight, input_lengths, nbest, final_norm, max_len,
-                                   mbr_scale)
+                                   mbr_scale, lm, lm_weight, token_bonus)
 
     def token_drop_ids(self, bos_token_id=1):
         """The ids that are no labels: (BOS, EOS, PAD) and the CTC blank where it is another id.  As `drop` they

@@ -226,5 +226,7 @@ def mbr_rerank(result, scale=1.0, drop=(), stop=None):
 
     out = (pick(tokens), pick(lengths), pick(scores))
     if isinstance(result, RescoreResult):
-        return RescoreResult(*out, pick(result.att_scores), pick(result.ctc_scores), risk.gather(1, order))
+        lm_scores = getattr(result, "lm_scores", None)
+        return RescoreResult(*out, pick(result.att_scores), pick(result.ctc_scores), risk.gather(1, order),
+                             None if lm_scores is None else pick(lm_scores))
     return MbrResult(*out, risk.gather(1, order))

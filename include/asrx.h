@@ -37,7 +37,8 @@ extern "C" {
  * 6: joint CTC/attention beam search: asrx_ctc_prefix_init, asrx_ctc_prefix_score, asrx_ctc_prefix_advance,
  * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
  * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words.  9: token error rates and
- * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank). */
+ * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank.  10: n-gram LM shallow fusion: asrx_ngram_score,
+ * asrx_ngram_advance, asrx_ngram_seq_logprob). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -532,7 +533,7 @@ int asrx_ctc_prefix_advance(const float* logp, const int32_t* frames, int32_t B,
  * multiply-adds, fp32; extra fp32 [B*W][ld_extra >= V], columns [0, V) read; NaN reads as -inf).  A finished beam
  * still offers exactly (w, eos) at score_in[w]; order, outputs, limits and the LDS / re-read paths are those of
  * asrx_beam_step, which att_weight = 1, extra_weight = 0 over a zero matrix reproduces bit for bit.  The operand is
- * generic: the CTC prefix scores here, a language model's later. */
+ * generic: the CTC prefix scores, a language model's (asrx_ngram_score, version 10), or both fused by that launch. */
 int asrx_beam_step_joint(const float* logits, int32_t B, int32_t W, int32_t V, int64_t ld, const float* extra,
                          int64_t ld_extra, float att_weight, float extra_weight, const float* score_in,
                          const uint8_t* fin_in, const int32_t* len_in, int64_t eos, float* score_out, int64_t* tok_out,
@@ -662,6 +663,64 @@ int asrx_edit_distance(const int64_t* hyp, int64_t ld_hyp, int32_t hyp_cols, con
  * One wave per sample, one launch; graph-capturable, deterministic. */
 int asrx_mbr_rank(const int32_t* dist, const float* score, const int32_t* n_hyp, int32_t B, int32_t W, float scale,
                   float* risk, int32_t* order, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * N-gram language model on the device (version >= 10): the `extra` operand of asrx_beam_step_joint for shallow fusion
+ * in beam search, and whole-sequence LM scores for two-pass rescoring.  A back-off n-gram over the model's token ids.
+ * The table (host-built, device-resident, natural-log units) is a forward trie in breadth-first order:
+ *   node 0 the empty context; nodes 1 .. V the unigrams, dense (token v is node 1 + v, present for every id; ids the
+ *   model does not cover carry its out-of-vocabulary log-probability); higher orders level by level, so the children
+ *   of a node are contiguous and sorted by ascending token.
+ *   first_child int32 [n_nodes + 1]   the children of node i are the nodes [first_child[i], first_child[i + 1])
+ *   token       int32 [n_nodes]
+ *   logp        fp32  [n_nodes]       log p(token | the context the parent spells)
+ *   backoff     fp32  [n_nodes]       log back-off weight of the context the node spells, 0 where the model has none
+ *   n_nodes > V, 1 <= order <= ASRX_NGRAM_MAX_ORDER, 1 <= V <= 2^20 (above: ASRX_ERR_UNSUPPORTED)
+ * Hypothesis state: ctx int32 [R][order - 1]; ctx[r][k - 1] = the node that spells the last k tokens of hypothesis r,
+ * or -1 if that k-gram is not in the table.  The orders are looked up independently ("a b c" may exist without
+ * "b c").  The root state is data the caller writes: ctx[r][0] = 1 + bos (-1 without a sentence-start token), the
+ * rest -1.  With k* the largest k in 0 .. order - 1 such that k = 0, or ctx[r][k - 1] is valid and has a child with
+ * token v:
+ *   lm(v) = logp[that child] + sum over the valid j > k* of backoff[ctx[r][j - 1]]       (k* = 0: logp[1 + v])
+ * the back-off weights added to logp one by one in ascending j, in fp32.
+ * The host never reads the table, and the kernels are memory-safe against a malformed one: a ctx entry outside
+ * [0, n_nodes) reads as -1, a child range is clamped to [0, n_nodes], a token[] value outside [0, V) is skipped and
+ * never used as an index.  No workspace, allocation or synchronisation; graph-capturable; no floating-point atomics,
+ * so the same inputs give the same bits.  Every count, order, V, ld, non-finite weight and null pointer is refused
+ * with ASRX_ERR_ARG before any device access; B, R or N = 0 returns 0.
+ * ------------------------------------------------------------------------------------------------- */
+#define ASRX_NGRAM_MAX_ORDER 6
+#define ASRX_NGRAM_LDS_V 8192   /* asrx_ngram_score builds rows of up to this many columns in LDS */
+
+/* Once per step (one launch, one workgroup per slot): out[r][v] = base_weight * base[r][v] + lm_weight * lm(v) + bonus
+ * for v < V (fp32 rows of stride ld_out >= V; columns [V, ld_out) are not written).  base (fp32 [R][ld_base >= V]) is
+ * nullable, and a zero weight drops its term (also lm_weight = 0 the LM term), so there is no 0 * -inf.  out must not
+ * overlap base.  The row is built by filling the unigram level and overwriting, order by order, the columns of each
+ * existing context's children, a workgroup barrier between two orders; in LDS for V <= ASRX_NGRAM_LDS_V, else in
+ * the out row itself. */
+int asrx_ngram_score(const int32_t* first_child, const int32_t* token, const float* logp, const float* backoff,
+                     int32_t n_nodes, int32_t order, int32_t V, const int32_t* ctx, int32_t R, const float* base,
+                     int64_t ld_base, float base_weight, float lm_weight, float bonus, float* out, int64_t ld_out,
+                     void* stream);
+/* Once per step after the selection (one launch): slot j of sample b extends slot parent[j] by tok[j], the contract
+ * of asrx_ctc_prefix_advance (parent int32 in [0, W), tok int64, fin_prev uint8 [B*W] the selection's fin_in): a
+ * finished parent or tok == eos copies the parent's state; otherwise ctx_out[j][0] = 1 + tok and ctx_out[j][k - 1] =
+ * the child of ctx_in[parent][k - 2] with token tok for k >= 2 (binary search over the sorted child list; -1 if there
+ * is none, or for a token outside [0, V)).  W >= 1, 0 <= eos < V; ctx_out must not overlap ctx_in. */
+int asrx_ngram_advance(const int32_t* first_child, const int32_t* token, const float* logp, const float* backoff,
+                       int32_t n_nodes, int32_t order, int32_t V, int32_t B, int32_t W, int32_t eos,
+                       const int32_t* parent, const int64_t* tok, const uint8_t* fin_prev, const int32_t* ctx_in,
+                       int32_t* ctx_out, void* stream);
+/* Whole sequences (one launch, one workgroup per row): tgt int64 [N][ld_tgt >= L] as for asrx_seq_logprob.
+ * lm_out[n] = the sum, in position order, of log p(tgt[n][i] | bos, the earlier scored tokens) (bos = -1: no
+ * sentence-start token); positions equal to `ignore` or outside [0, V) are skipped and do not enter the context.
+ * out[n] = add_scale * add[n] + lm_weight * lm_out[n] + bonus * (scored positions); add (fp32 [N]) is nullable, and
+ * a zero scale drops its term.  With n_hyp (int32 [N / W], nullable) row n = b*W + j is dead for j >= n_hyp[b]: -inf
+ * in both outputs, its row is not read.  L <= 4096 (above: ASRX_ERR_UNSUPPORTED). */
+int asrx_ngram_seq_logprob(const int32_t* first_child, const int32_t* token, const float* logp, const float* backoff,
+                           int32_t n_nodes, int32_t order, int32_t V, const int64_t* tgt, int64_t ld_tgt, int32_t N,
+                           int32_t L, int64_t ignore, int32_t bos, const int32_t* n_hyp, int32_t W, const float* add,
+                           float add_scale, float lm_weight, float bonus, float* lm_out, float* out, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
