@@ -7,6 +7,7 @@ native library and a GPU.
 from .layers import MHA, FeedForward, LayerNorm, TrainablePositionalEncoding  # noqa: F401
 from .functions import BeamResult, RescoreResult  # noqa: F401
 from .kernels import CtcAlignment  # noqa: F401
+from .augment import SpecAugment  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
 from .lm import NgramLM  # noqa: F401
 from .model import Decoder, DecoderLayer, Encoder, EncoderLayer, FrontEnd, Transformer, subsampled  # noqa: F401

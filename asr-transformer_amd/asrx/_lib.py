@@ -182,12 +182,17 @@ SIGNATURES = {
                            c_vp, c_vp],
     "asrx_ngram_seq_logprob": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_i32, c_i64, c_i32,
                                c_vp, c_i32, c_vp, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp],
+    # (src, dst, B, F, T, batch strides, lengths, nF, Wf, nT, Wt, time_ratio, W, mask_value, seed, step, plan_out)
+    "asrx_specaug": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32,
+                     c_f32, c_u64, c_u64, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
 ED_PAIRS, ED_GROUP, ED_CROSS = 0, 1, 2    # asrx_edit_distance pairing modes
 CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended states)
 NGRAM_MAX_ORDER = 6         # ASRX_NGRAM_MAX_ORDER
+SPECAUG_MAX_MASKS = 8       # ASRX_SPECAUG_MAX_MASKS
+SPECAUG_RUN = 1024          # ASRX_SPECAUG_RUN: frames one workgroup of asrx_specaug covers
 
 ERRORS = {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}
 

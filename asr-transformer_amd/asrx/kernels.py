@@ -938,6 +938,36 @@ def step_tokens(text, inp, mask):
     return dec_in, tgt, valid
 
 
+def _planes(t, name):
+    """(batch stride in elements) of an fp32 (B, 1, F, T) tensor whose (F, T) planes are dense, time innermost."""
+    if t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 1:
+        raise ValueError(f"asrx: {name} must be fp32 (B, 1, F, T), got {t.dtype} {tuple(t.shape)}")
+    F, T = t.shape[2], t.shape[3]
+    if (T > 1 and t.stride(3) != 1) or (F > 1 and t.stride(2) != T) or (t.shape[0] > 1 and t.stride(0) < F * T):
+        raise ValueError(f"asrx: {name} must have dense (F, T) planes, time innermost (strides {t.stride()})")
+    return t.stride(0) if t.shape[0] > 1 else F * T
+
+
+def specaug(src, dst, *, lengths=None, freq_masks=0, freq_width=0, time_masks=0, time_width=0, time_ratio=1.0,
+            time_warp=0, mask_value=0.0, seed=0, step=0, plan_out=None):
+    """dst = SpecAugment(src) of step `step` in one launch (asrx_specaug; the rule is DESIGN.md §16): fp32
+    (B, 1, F, T), src and dst disjoint; lengths int32 [B] or None; plan_out int32 [B, 4 + 2 * (freq_masks +
+    time_masks)] or None."""
+    _cuda(src, dst, lengths, plan_out)
+    sb, db = _planes(src, "src"), _planes(dst, "dst")
+    if src.shape != dst.shape:
+        raise ValueError(f"asrx: specaug shapes differ: {tuple(src.shape)} vs {tuple(dst.shape)}")
+    B, _, F, T = src.shape
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == B
+    if plan_out is not None:
+        assert plan_out.dtype == torch.int32 and plan_out.is_contiguous()
+        assert plan_out.numel() == B * (4 + 2 * (freq_masks + time_masks))
+    call("asrx_specaug", src.data_ptr(), dst.data_ptr(), B, F, T, sb, db, _p(lengths), freq_masks, freq_width,
+         time_masks, time_width, time_ratio, time_warp, mask_value, int(seed) & _U64, int(step) & _U64, _p(plan_out),
+         stream())
+
+
 def dropout_mask(n, p, seed, device):
     keep = torch.empty(n, dtype=torch.uint8, device=device)
     call("asrx_dropout_mask", keep.data_ptr(), n, p, seed & _U64, stream())

@@ -14,12 +14,16 @@ issued between segment replays, so it still overlaps the rest of the backward.
 
 `Trainer(..., ctc_weight=w)` on a `Transformer(..., ctc=True)` trains the hybrid objective (1 - w) * CE + w * CTC:
 the CTC launches (head GEMM, asrx_ctc_targets, asrx_ctc_loss, head data gradient) join the same captured chain.
+
+`Trainer(..., spec_augment=asrx.SpecAugment(...))` trains step n on step n's SpecAugment of its spectrogram: one
+asrx_specaug launch that takes the place of the spectrogram's copy into the captured input buffer.
 """
 import os
 
 import torch
 
 from . import kernels as K
+from .augment import rank_seed
 from .blocks import FreshGrads
 from .dist import GradAllReduce
 from .functions import get_store, make_ctx, model_backward, model_forward
@@ -156,6 +160,14 @@ def _minus(a, b, holes, align=1):
     return out
 
 
+def reducer_rank(reducer):
+    """This process's rank in the reducer's group (0 without a process group; an injected all-reduce may carry its
+    own `rank`, as it may carry `world`)."""
+    if reducer.allreduce_fn is not None:
+        return int(getattr(reducer.allreduce_fn, "rank", 0))
+    return torch.distributed.get_rank(reducer.group) if torch.distributed.is_initialized() else 0
+
+
 def unused_params(model):
     """Parameters the reference's forward never uses, so they never get a gradient there (their .grad stays None and
     torch's optimizers skip them): input_encoding (model.py:173) and Encoder._norm_in (model.py:12)."""
@@ -243,7 +255,11 @@ def train_epoch_native(trainer, data_loader, device=None):
         text = batch["text"].to(dev)
         mask = batch["mask"].to(dev)
         input_text, mask = shift_inputs(text, mask)
-        loss = trainer.step(spectrum, text, mask, input_text=input_text)
+        if trainer.spec_augment is not None and "spectrum_mask" in batch:
+            loss = trainer.step(spectrum, text, mask, input_text=input_text,
+                                input_lengths=batch["spectrum_mask"].to(dev).sum(-1))
+        else:
+            loss = trainer.step(spectrum, text, mask, input_text=input_text)
         total += loss.reshape(())                      # before the next step overwrites a replayed graph's output
         B, L = text.shape[0], text.shape[1] - 1
         preds.append(trainer.last_preds.view(B, L).clone())
@@ -289,8 +305,13 @@ class Trainer:
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.98), eps=1e-9, weight_decay=0.0, decoupled=True,
                  ignore_index=-100, group=None, bucket_mb=64, allreduce_fn=None, graph=None, wire=None, preds=False,
-                 ctc_weight=0.0, bos_token_id=1):
+                 ctc_weight=0.0, bos_token_id=1, spec_augment=None):
         self.model = model
+        # spec_augment (asrx.SpecAugment): step n (1-based, the replay's seed offset) trains on the augmentation of
+        # step n of its spectrogram, one asrx_specaug launch: into a buffer of the trainer's in an eager step, into the
+        # captured input buffer, in place of the copy, before a replay.  None: the step launch for launch as without.
+        self.spec_augment = spec_augment
+        self._aug_buf = None
         # ctc_weight w > 0: the hybrid objective (1 - w) * CE + w * CTC_mean, the CTC term on the model's ctc_head
         # (Transformer(..., ctc=True)) over all T' encoder frames, its targets the step's text without BOS / EOS / PAD
         # (asrx_ctc_targets), zero_infinity on.  w = 0 is the cross-entropy step, launch for launch; a ctc_head the
@@ -466,10 +487,23 @@ class Trainer:
             self._adam(hyp, sp)
         main.wait_stream(side)
 
-    def step(self, spectrum, text, mask, input_text=None):
+    def _aug_seed(self):
+        """The augmenter's seed on this data-parallel rank (asrx.augment.rank_seed)."""
+        return rank_seed(self.spec_augment.seed, reducer_rank(self.reducer))
+
+    def _augment(self, spectrum, out, input_lengths, n):
+        """Step n's augmentation of the caller's spectrogram into `out` (None: the eager steps' own buffer)."""
+        if out is None:
+            out = self._aug_buf
+            if out is None or out.shape != spectrum.shape or out.device != spectrum.device:
+                out = self._aug_buf = torch.empty(tuple(spectrum.shape), dtype=torch.float32, device=spectrum.device)
+        return self.spec_augment.augment(spectrum, out=out, lengths=input_lengths, step=n, seed=self._aug_seed())
+
+    def step(self, spectrum, text, mask, input_text=None, input_lengths=None):
         """One training step (forward, CE, backward, all-reduce, AdamW).  Returns the loss as a device scalar; in
         graph mode it is the captured output tensor, overwritten by the next step.  input_text: see
-        forward_backward."""
+        forward_backward.  input_lengths (optional, [B]): the valid frames of each spectrogram, for the augmenter
+        (Trainer(..., spec_augment=...)); the caller's spectrogram is never written."""
         if input_text is None:
             input_text = text
         if self.graph and self.model.precision == "bf16":
@@ -480,8 +514,10 @@ class Trainer:
                 self._capture(spectrum, text, mask, input_text)
                 self._caps[key] = self._cap
             if self._cap is not None:
-                return self._replay(spectrum, text, mask, input_text)
+                return self._replay(spectrum, text, mask, input_text, input_lengths)
             self._eager_keys.add(key)
+        if self.spec_augment is not None:
+            spectrum = self._augment(spectrum, None, input_lengths, self.step_count + 1)
         self._fuse_next = self._fused_adam_ok()
         # this step's lr / bias corrections from the device, as in a replayed graph (and the fused launch): every
         # AdamW of the trainer takes 1/sqrt(bias_corr2) from the same device arithmetic
@@ -537,11 +573,17 @@ class Trainer:
         torch.cuda.synchronize(dev)
         self._cap = (seg, ins, loss, self.last_preds)
 
-    def _replay(self, spectrum, text, mask, input_text):
+    def _replay(self, spectrum, text, mask, input_text, input_lengths=None):
         seg, ins, loss, preds = self._cap
+        aug = self.spec_augment is not None
+        if aug and ins[0].data_ptr() == spectrum.data_ptr():
+            raise ValueError("Trainer.step: the spectrogram is the captured input buffer itself; the augmenter does not "
+                             "work in place, pass a tensor of your own")
         self.last_preds = preds
-        for dst, src in zip(ins, (spectrum, text, mask, input_text)):
-            if dst.data_ptr() != src.data_ptr():
+        for i, (dst, src) in enumerate(zip(ins, (spectrum, text, mask, input_text))):
+            if i == 0 and aug:   # the augmenting launch is this buffer's copy
+                self._augment(src, dst, input_lengths, self.step_count + 1)
+            elif dst.data_ptr() != src.data_ptr():
                 dst.copy_(src, non_blocking=True)
         self.step_count += 1
         K.set_seed_offset(self.step_count)

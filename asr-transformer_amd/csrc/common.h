@@ -119,14 +119,15 @@ ASRX_DEV uint32_t rng_hash(uint64_t seed, uint32_t pidx) {
 // the seed unchanged.  One copy per translation unit (no relocatable device code): asrx_set_seed_offset sets
 // every copy with ONE launch, through the copies' device addresses (ASRX_SEED_OFFSET_SETTER exports each TU's).
 static __device__ uint64_t g_seed_offset;
-ASRX_DEV uint64_t seed_eff(uint64_t seed) {
-  const uint64_t o = g_seed_offset;
+// the seed of offset o (three multiplies; offset 0 = the seed unchanged).  asrx_specaug takes its step by value here.
+ASRX_DEV uint64_t seed_at(uint64_t seed, uint64_t o) {
   if (o == 0) return seed;
   uint64_t z = o * 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return seed ^ z ^ (z >> 31);
 }
+ASRX_DEV uint64_t seed_eff(uint64_t seed) { return seed_at(seed, g_seed_offset); }
 #define ASRX_SEED_OFFSET_SETTER(tu)                                                                 \
   uint64_t* asrx_seed_offset_addr_##tu() {                                                          \
     void* p = nullptr;                                                                              \

@@ -38,7 +38,7 @@ extern "C" {
  * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
  * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words.  9: token error rates and
  * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank.  10: n-gram LM shallow fusion: asrx_ngram_score,
- * asrx_ngram_advance, asrx_ngram_seq_logprob). */
+ * asrx_ngram_advance, asrx_ngram_seq_logprob.  11: SpecAugment while the spectrogram is copied: asrx_specaug). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -721,6 +721,36 @@ int asrx_ngram_seq_logprob(const int32_t* first_child, const int32_t* token, con
                            int32_t n_nodes, int32_t order, int32_t V, const int64_t* tgt, int64_t ld_tgt, int32_t N,
                            int32_t L, int64_t ignore, int32_t bos, const int32_t* n_hyp, int32_t W, const float* add,
                            float add_scale, float lm_weight, float bonus, float* lm_out, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * SpecAugment while the spectrogram is copied (version >= 11): a time warp, then frequency and time masks, one launch.
+ * src, dst: fp32 [B][F][T], time innermost, rows T apart, utterances src_bstride / dst_bstride elements apart
+ * (>= F * T); lengths (int32 [B], nullable): valid frames, L = clamp(lengths[b], 0, T), T without it.
+ * s = seed for step 0, else the seed of offset `step` (the mix asrx_set_seed_offset's readers apply; step comes by
+ * value, the device-resident offset is not read).  D = 2 + 2 * (freq_masks + time_masks); draw j of utterance b is
+ * h = rng_hash(s, b * D + j); U[0, n) = (uint64(h) * n) >> 32.  A draw that is not taken leaves the others' indices.
+ *   warp (draws 0, 1; only if time_warp = W > 0 and L > 2W): w0 = W + U[0, L - 2W), c = w0 - W + 1 + U[0, 2W); output
+ *     frame t < L reads position base + num / den: (0, t * w0, c) for t < c, else (w0, (t - c) * (L - w0), L - c);
+ *     i = base + num / den and r = num % den in integers, frac = float(r) / float(den),
+ *     out[f][t] = a + frac * (b - a) with a = x[f][i], b = x[f][min(i + 1, L - 1)]
+ *   frequency mask j (draws 2 + 2j, 3 + 2j): w = U[0, min(freq_width, F) + 1), f0 = U[0, F - w + 1); rows
+ *     [f0, f0 + w) take mask_value on frames [0, L)
+ *   time mask j (draws 2 + 2 freq_masks + 2j, + 1): cap = min(time_width, (int)floorf(time_ratio * (float)L)),
+ *     w = U[0, cap + 1), t0 = U[0, L - w + 1); output frames [t0, t0 + w) take mask_value in every row
+ *   frames t >= L are copied bit for bit.
+ * plan_out (int32 [B][4 + 2 * (freq_masks + time_masks)], nullable): L, w0, c (0, 0 without a warp), 0, the (f0, w)
+ * pairs, the (t0, w) pairs.  Masked elements are not read; without a warp, 16-B aligned rows (both bases, both
+ * strides and T multiples of 4 elements) move 16 B per lane.  A workgroup covers ASRX_SPECAUG_RUN frames.
+ * Before any device access: a null, misaligned, equal or overlapping src / dst, F < 1, T < 1, a negative count or
+ * width, a batch stride below F * T or time_ratio outside [0, 1] return ASRX_ERR_ARG; more than
+ * ASRX_SPECAUG_MAX_MASKS masks of a kind, B > 65535 or F > 262140 ASRX_ERR_UNSUPPORTED; B = 0 returns 0.
+ * ------------------------------------------------------------------------------------------------- */
+#define ASRX_SPECAUG_MAX_MASKS 8
+#define ASRX_SPECAUG_RUN 1024
+int asrx_specaug(const float* src, float* dst, int32_t B, int32_t F, int32_t T, int64_t src_bstride,
+                 int64_t dst_bstride, const int32_t* lengths, int32_t freq_masks, int32_t freq_width,
+                 int32_t time_masks, int32_t time_width, float time_ratio, int32_t time_warp, float mask_value,
+                 uint64_t seed, uint64_t step, int32_t* plan_out, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
