@@ -185,6 +185,18 @@ SIGNATURES = {
     # (src, dst, B, F, T, batch strides, lengths, nF, Wf, nT, Wt, time_ratio, W, mask_value, seed, step, plan_out)
     "asrx_specaug": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32,
                      c_f32, c_u64, c_u64, c_vp, c_vp],
+    # (asrx_spectrogram's arguments with wave_lengths after batch_stride; fb, fb_range (HOST), n_mels, log_mode,
+    #  log_mul, log_eps, mean, istd, pad_value; ws, ws_elems, out, frame_lengths)
+    "asrx_logmel": [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32,
+                    c_f32, c_f32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp],
+    # (ws, batch, frames, wave_lengths, n_fft, hop, nbins, power, scale, then as asrx_logmel from fb to pad_value;
+    #  out, frame_lengths)
+    "asrx_logmel_pass": [c_vp, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32, c_f32,
+                         c_f32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp],
+    "asrx_stft_power": [c_vp, c_i64, c_i64, c_i32, c_i32, c_f32, c_vp, c_vp],
+    # (x, out, B, F, T, batch strides, lengths, mean, istd, norm_var, eps, pad_value)
+    "asrx_cmvn": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp],
+    "asrx_feature_stats": [c_vp, c_i32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 CTC_SUM, CTC_MEAN = 0, 1    # asrx_ctc_loss reduction codes
@@ -193,6 +205,7 @@ CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended s
 NGRAM_MAX_ORDER = 6         # ASRX_NGRAM_MAX_ORDER
 SPECAUG_MAX_MASKS = 8       # ASRX_SPECAUG_MAX_MASKS
 SPECAUG_RUN = 1024          # ASRX_SPECAUG_RUN: frames one workgroup of asrx_specaug covers
+LOGMEL_MAX_MELS = 256       # ASRX_LOGMEL_MAX_MELS
 
 ERRORS = {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}
 

@@ -968,6 +968,107 @@ def specaug(src, dst, *, lengths=None, freq_masks=0, freq_width=0, time_masks=0,
          stream())
 
 
+def _feat3(t, name):
+    """(B, F, T, batch stride) of an fp32 feature tensor (B, F, T) or (B, 1, F, T) with dense (F, T) planes."""
+    if t.dtype != torch.float32 or t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[1] != 1):
+        raise ValueError(f"asrx: {name} must be fp32 (B, F, T) or (B, 1, F, T), got {t.dtype} {tuple(t.shape)}")
+    B, F, T = t.shape[0], t.shape[-2], t.shape[-1]
+    if (T > 1 and t.stride(-1) != 1) or (F > 1 and t.stride(-2) != T) or (B > 1 and t.stride(0) < F * T):
+        raise ValueError(f"asrx: {name} must have dense (F, T) planes, time innermost (strides {t.stride()})")
+    return B, F, T, (t.stride(0) if B > 1 else F * T)
+
+
+def _lengths(lengths, B):
+    if lengths is not None:
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() == B
+    return _p(lengths)
+
+
+def logmel(audio, basis, fb, fb_range, out, ws, *, n_fft, hop, power=2, scale=1.0, wave_lengths=None, log_mode=0,
+           log_mul=1.0, log_eps=1e-6, mean=None, istd=None, pad_value=0.0, frame_lengths=None):
+    """out (B, n_mels, frames) = the (log-)mel features of fp32 audio (B, samples) in one call (asrx_logmel, DESIGN.md
+    §17): basis as asrx.features.dft_basis, fb fp32 (nbins, n_mels) on the device, fb_range int32 (n_mels, 2) on the
+    HOST (asrx.features.filterbank_ranges), ws fp32 with >= B * frames * 2 * nbins elements; wave_lengths and
+    frame_lengths int32 [B] or None; mean / istd fp32 [n_mels] or None."""
+    _cuda(audio, basis, fb, out, ws, wave_lengths, mean, istd, frame_lengths)
+    if fb_range.is_cuda or fb_range.dtype != torch.int32 or not fb_range.is_contiguous():
+        raise ValueError("asrx: fb_range must be a contiguous int32 host tensor")
+    B, S = audio.shape
+    nbins, n_mels = fb.shape
+    assert audio.dtype == torch.float32 and (S == 1 or audio.stride(1) == 1)
+    assert fb.dtype == torch.float32 and fb.is_contiguous() and tuple(fb_range.shape) == (n_mels, 2)
+    assert basis.dtype == torch.float32 and basis.is_contiguous() and tuple(basis.shape) == (2 * nbins, n_fft)
+    frames = (S - n_fft) // hop + 1 if S >= n_fft else 0
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, n_mels, frames)
+    for v in (mean, istd):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n_mels)
+    if frame_lengths is not None:
+        assert frame_lengths.dtype == torch.int32 and frame_lengths.is_contiguous() and frame_lengths.numel() == B
+    call("asrx_logmel", audio.data_ptr(), B, S, audio.stride(0), _lengths(wave_lengths, B), basis.data_ptr(), n_fft,
+         hop, nbins, power, scale, fb.data_ptr(), fb_range.data_ptr(), n_mels, log_mode, log_mul, log_eps, _p(mean),
+         _p(istd), pad_value, ws.data_ptr(), ws.numel(), out.data_ptr(), _p(frame_lengths), stream())
+
+
+def logmel_pass(ws, fb, fb_range, out, *, n_fft, hop, power=2, scale=1.0, wave_lengths=None, log_mode=0, log_mul=1.0,
+                log_eps=1e-6, mean=None, istd=None, pad_value=0.0, frame_lengths=None):
+    """asrx_logmel's second pass alone (asrx_logmel_pass): ws fp32 (B, frames, 2 * nbins) as a DFT GEMM left it ->
+    out (B, n_mels, frames); the other arguments as logmel's."""
+    _cuda(ws, fb, out, wave_lengths, mean, istd, frame_lengths)
+    nbins, n_mels = fb.shape
+    B, frames = out.shape[0], out.shape[2]
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= B * frames * 2 * nbins
+    assert fb.dtype == torch.float32 and fb.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
+    assert out.shape[1] == n_mels and not fb_range.is_cuda and fb_range.dtype == torch.int32
+    assert fb_range.is_contiguous() and tuple(fb_range.shape) == (n_mels, 2)
+    for v in (mean, istd):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n_mels)
+    if frame_lengths is not None:
+        assert frame_lengths.dtype == torch.int32 and frame_lengths.is_contiguous() and frame_lengths.numel() == B
+    call("asrx_logmel_pass", ws.data_ptr(), B, frames, _lengths(wave_lengths, B), n_fft, hop, nbins, power, scale,
+         fb.data_ptr(), fb_range.data_ptr(), n_mels, log_mode, log_mul, log_eps, _p(mean), _p(istd), pad_value,
+         out.data_ptr(), _p(frame_lengths), stream())
+
+
+def stft_power(ws, out, *, power=2, scale=1.0):
+    """asrx_spectrogram's second pass alone (asrx_stft_power): ws fp32 (B, frames, 2 * nbins) -> out (B, nbins,
+    frames) = scale * (re^2 + im^2)^(power / 2)."""
+    _cuda(ws, out)
+    B, nbins, frames = out.shape
+    assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= B * frames * 2 * nbins
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    call("asrx_stft_power", ws.data_ptr(), B, frames, nbins, power, scale, out.data_ptr(), stream())
+
+
+def cmvn(x, out, *, lengths=None, mean=None, istd=None, norm_var=True, eps=1e-5, pad_value=0.0):
+    """out = CMVN(x) over the valid frames (asrx_cmvn): fp32 (B, F, T) or (B, 1, F, T); out may be x.  Without `mean`
+    the statistics are each (b, f) row's own; with it (and optionally istd), fp32 [F] given ones."""
+    _cuda(x, out, lengths, mean, istd)
+    B, F, T, xb = _feat3(x, "x")
+    Bo, Fo, To, ob = _feat3(out, "out")
+    if (B, F, T) != (Bo, Fo, To):
+        raise ValueError(f"asrx: cmvn shapes differ: {tuple(x.shape)} vs {tuple(out.shape)}")
+    for v in (mean, istd):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == F)
+    if B * F * T == 0:
+        return
+    call("asrx_cmvn", x.data_ptr(), out.data_ptr(), B, F, T, xb, ob, _lengths(lengths, B), _p(mean), _p(istd),
+         int(bool(norm_var)), eps, pad_value, stream())
+
+
+def feature_stats(x, total, total_sq, count, *, lengths=None):
+    """total[f] += sum x, total_sq[f] += sum x^2 (fp64 [F]), count[0] += frames (int64 [1]) over the valid frames of
+    fp32 (B, F, T) or (B, 1, F, T) (asrx_feature_stats)."""
+    _cuda(x, total, total_sq, count, lengths)
+    B, F, T, xb = _feat3(x, "x")
+    assert total.dtype == torch.float64 and total_sq.dtype == torch.float64 and count.dtype == torch.int64
+    assert total.is_contiguous() and total_sq.is_contiguous() and total.numel() == F and total_sq.numel() == F
+    assert count.numel() == 1
+    if B * F * T == 0:
+        return
+    call("asrx_feature_stats", x.data_ptr(), B, F, T, xb, _lengths(lengths, B), total.data_ptr(), total_sq.data_ptr(),
+         count.data_ptr(), stream())
+
+
 def dropout_mask(n, p, seed, device):
     keep = torch.empty(n, dtype=torch.uint8, device=device)
     call("asrx_dropout_mask", keep.data_ptr(), n, p, seed & _U64, stream())

@@ -81,3 +81,17 @@ extern "C" int asrx_spectrogram(const float* audio, int64_t batch, int64_t sampl
   ASRX_CHECK_LAUNCH();
   return ASRX_OK;
 }
+
+// asrx_spectrogram's second pass alone, on a workspace a DFT GEMM has filled (tools/fbank_bench.py times it against
+// asrx_logmel_pass, which replaces it)
+extern "C" int asrx_stft_power(const float* ws, int64_t batch, int64_t frames, int32_t nbins, int32_t power,
+                               float scale, float* out, void* stream) {
+  if (!ws || !out || batch < 0 || frames < 1 || nbins < 1 || (power != 1 && power != 2)) return ASRX_ERR_ARG;
+  if (batch == 0) return ASRX_OK;
+  if (batch > 65535 || frames > 0x7fffffffLL) return ASRX_ERR_UNSUPPORTED;
+  const dim3 grid((unsigned)((frames + PT - 1) / PT), (unsigned)((nbins + PT - 1) / PT), (unsigned)batch);
+  hipLaunchKernelGGL(stft_power_kernel, grid, dim3(256), 0, (hipStream_t)stream, ws, frames, (int)nbins,
+                     frames * 2 * (int64_t)nbins, out, (int64_t)nbins * frames, (int)power, scale);
+  ASRX_CHECK_LAUNCH();
+  return ASRX_OK;
+}

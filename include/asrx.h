@@ -38,7 +38,9 @@ extern "C" {
  * asrx_beam_step_joint.  7: two-pass decoding: asrx_ctc_prefix_beam, asrx_hyp_tokens, asrx_seq_logprob,
  * asrx_rescore_rank.  8: forced alignment: asrx_ctc_align, asrx_ctc_align_workspace_words.  9: token error rates and
  * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank.  10: n-gram LM shallow fusion: asrx_ngram_score,
- * asrx_ngram_advance, asrx_ngram_seq_logprob.  11: SpecAugment while the spectrogram is copied: asrx_specaug). */
+ * asrx_ngram_advance, asrx_ngram_seq_logprob.  11: SpecAugment while the spectrogram is copied: asrx_specaug.
+ * 12: log-mel filterbank features and CMVN: asrx_logmel, asrx_logmel_pass, asrx_stft_power, asrx_cmvn,
+ * asrx_feature_stats). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -751,6 +753,65 @@ int asrx_specaug(const float* src, float* dst, int32_t B, int32_t F, int32_t T, 
                  int64_t dst_bstride, const int32_t* lengths, int32_t freq_masks, int32_t freq_width,
                  int32_t time_masks, int32_t time_width, float time_ratio, int32_t time_warp, float mask_value,
                  uint64_t seed, uint64_t step, int32_t* plan_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Log-mel filterbank features and CMVN (version >= 12).
+ *
+ * asrx_logmel: waveform -> (log-)mel features, the STFT of asrx_spectrogram (same arguments, same fp32 GEMM into ws)
+ * followed by ONE pass that reads ws once and stores out; the nbins-wide power spectrogram is never written.
+ *   wave_lengths  int32 [batch], nullable (device): valid samples of each row; frames_b = len >= n_fft ?
+ *                 (len - n_fft) / hop + 1 : 0, clamped to frames = (samples - n_fft) / hop + 1; null: frames
+ *   fb            fp32 [nbins][n_mels] (device), any real matrix
+ *   fb_range      int32 [n_mels][2] in HOST memory, read during the call: the half-open bin range [lo, hi) outside
+ *                 which column m of fb is zero ([0, nbins) for a dense one).  The kernel sums
+ *                 p[n] * fb[n][m] over n = lo .. hi - 1 in ascending order in fp32 (fused multiply-adds) and nothing
+ *                 else, p[n] = scale * (re^2 + im^2)^(power / 2); lo == hi gives energy 0
+ *   log_mode      0: v = e;  1: v = log_mul * logf(e + log_eps);  2: v = log_mul * logf(fmaxf(e, log_eps))
+ *                 (log_mul 1 for ln, 1 / ln 10 for log10)
+ *   mean, istd    fp32 [n_mels], nullable (device): v = (v - mean[m]) * istd[m]; mean alone subtracts only
+ *   pad_value     every frame f >= frames_b of out, after the CMVN
+ *   out           fp32 [batch][n_mels][frames], time innermost (what the front end and asrx_specaug read)
+ *   frame_lengths int32 [batch], nullable (device): receives frames_b
+ * Workgroups whose 32 frames all lie at or beyond frames_b load nothing.  Before any device access: a null audio,
+ * basis, fb, fb_range, ws or out, a bad n_fft / hop / nbins / power, n_mels < 1, samples < n_fft, log_mode outside
+ * 0..2, log_eps <= 0 with a log mode, istd without mean, a range with lo < 0, lo > hi or hi > nbins, or a ws below
+ * batch * frames * 2 nbins elements return ASRX_ERR_ARG; n_mels > ASRX_LOGMEL_MAX_MELS, nbins > 65535,
+ * batch > 65535 or frames > 2^31 - 1 ASRX_ERR_UNSUPPORTED; batch = 0 returns 0.
+ *
+ * asrx_cmvn: out[b][f][t] = (x[b][f][t] - mean) * istd over t < L_b = clamp(lengths[b], 0, T) (T without lengths),
+ * pad_value on t >= L_b; x, out fp32 [B][F][T], rows T apart, utterances x_bstride / out_bstride apart (>= F * T).
+ *   mean == NULL (per utterance): per (b, f) row, mean = sum / L, var = sum((x - mean)^2) / L (two passes, never
+ *     E[x^2] - E[x]^2), istd = norm_var ? 1 / max(sqrt(var), eps) : 1; both sums in a fixed tree (deterministic)
+ *   mean != NULL (given statistics, global CMVN): mean[f], istd[f] (1 when istd is NULL); norm_var, eps unused
+ * out == x is allowed (in place, equal batch strides); any other overlap of the two extents, a null or misaligned
+ * pointer, F < 1, T < 1, B < 0, a batch stride below F * T, istd without mean or eps <= 0 where it is used return
+ * ASRX_ERR_ARG; B > 65535 ASRX_ERR_UNSUPPORTED; B = 0 returns 0.
+ *
+ * asrx_feature_stats: sum[f] += sum of x, sumsq[f] += sum of x^2 (fp64 [F] each) and count[0] += sum of L_b (int64)
+ * over the valid frames of x fp32 [B][F][T]; the accumulators are the caller's (zeroed by it), not atomic: calls on
+ * one accumulator set are ordered by the stream.  Fixed order, deterministic.
+ * ------------------------------------------------------------------------------------------------- */
+#define ASRX_LOGMEL_MAX_MELS 256
+int asrx_logmel(const float* audio, int64_t batch, int64_t samples, int64_t batch_stride, const int32_t* wave_lengths,
+                const float* basis, int32_t n_fft, int32_t hop, int32_t nbins, int32_t power, float scale,
+                const float* fb, const int32_t* fb_range, int32_t n_mels, int32_t log_mode, float log_mul,
+                float log_eps, const float* mean, const float* istd, float pad_value, float* ws, int64_t ws_elems,
+                float* out, int32_t* frame_lengths, void* stream);
+/* The two second passes alone, on a workspace ws ([batch][frames][2 nbins]) that a DFT GEMM has filled:
+ * asrx_logmel_pass is asrx_logmel without its GEMM (same arguments, `frames` given instead of derived, same checks),
+ * asrx_stft_power is asrx_spectrogram's square/transpose pass into out [batch][nbins][frames].  For callers that
+ * keep an STFT of their own, and for tools/fbank_bench.py, which times the one against the other. */
+int asrx_logmel_pass(const float* ws, int64_t batch, int64_t frames, const int32_t* wave_lengths, int32_t n_fft,
+                     int32_t hop, int32_t nbins, int32_t power, float scale, const float* fb, const int32_t* fb_range,
+                     int32_t n_mels, int32_t log_mode, float log_mul, float log_eps, const float* mean,
+                     const float* istd, float pad_value, float* out, int32_t* frame_lengths, void* stream);
+int asrx_stft_power(const float* ws, int64_t batch, int64_t frames, int32_t nbins, int32_t power, float scale,
+                    float* out, void* stream);
+int asrx_cmvn(const float* x, float* out, int32_t B, int32_t F, int32_t T, int64_t x_bstride, int64_t out_bstride,
+              const int32_t* lengths, const float* mean, const float* istd, int32_t norm_var, float eps,
+              float pad_value, void* stream);
+int asrx_feature_stats(const float* x, int32_t B, int32_t F, int32_t T, int64_t x_bstride, const int32_t* lengths,
+                       double* sum, double* sumsq, int64_t* count, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
