@@ -7,7 +7,8 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import CTC_MAX_TARGET, MAX_ROWSUM_GROUPS, AttnDesc, BF16, BITS, F32, GemmDesc, RowsumGroup, call
+from ._lib import (BF16, BITS, CONSTS, CTC_MAX_TARGET, CTC_MEAN, CTC_SUM, ED_CROSS, ED_GROUP, ED_PAIRS, F32,
+                   MAX_ROWSUM_GROUPS, AttnDesc, GemmDesc, GemmGroupDev, RowsumGroup, call)
 
 _U64 = (1 << 64) - 1
 
@@ -112,7 +113,8 @@ PROBE = None
 
 # asrx_gemm_desc.kernel: forced kernel family (0 = auto).  ASRX_GEMM_KERNEL picks a process-wide default (A/B).
 # The values are asrx.h's ASRX_GEMM_AUTO, _P3, _REG, _RING, _RING128, _P4, _WS and _WS64.
-KERNEL_CODES = {"auto": 0, "p3": 1, "reg": 3, "ring": 4, "ring128": 5, "p4": 6, "ws": 8, "ws64": 10}
+KERNEL_CODES = {k: CONSTS["ASRX_GEMM_" + k.upper()]
+                for k in ("auto", "p3", "reg", "ring", "ring128", "p4", "ws", "ws64")}
 GEMM_KERNEL = KERNEL_CODES.get(os.environ.get("ASRX_GEMM_KERNEL", "auto"), 0)
 
 
@@ -323,7 +325,8 @@ def xcd_plan(shapes, tile=256, nxcd=8, pack=None):
 
 
 # grouped launch: kind -> (tile, common->tile code: asrx.h's ASRX_GROUP_TILE_P3, _P4, _WS and _REG)
-_TILE_CODE = {"p3": ((256, 128), 3), "p4": ((256, 256), 4), "ws": ((256, 128), 5), "reg": ((128, 128), 128)}
+_TILE_CODE = {k: (tile, CONSTS["ASRX_GROUP_TILE_" + k.upper()])
+              for k, tile in (("p3", (256, 128)), ("p4", (256, 256)), ("ws", (256, 128)), ("reg", (128, 128)))}
 
 
 def upload(dst, host_bytes):
@@ -367,7 +370,7 @@ def _grouped_xcd(items, common, kind="p3", adam=None):
         if wgrad.stride(0) % 4 or wgrad.data_ptr() % 16:
             cvec = 0
     common.relu = cvec
-    queue = code == 5 and WGRAD_QUEUE and len(block_tile) % 8 == 0
+    queue = code == _TILE_CODE["ws"][1] and WGRAD_QUEUE and len(block_tile) % 8 == 0
     dev_ = items[0][0].device
     # the tile -> group and block -> tile maps depend on the shapes only: one device copy per plan, written outside
     # any graph capture and reused by every later call (a captured graph's launches point at it), so a step uploads
@@ -411,13 +414,14 @@ def _grouped_xcd(items, common, kind="p3", adam=None):
         common.rowsum_ws = part.data_ptr()
 
     fused = adam is not None and queue and common.beta == 0.0
+    groups = ctypes.cast(base, ctypes.POINTER(GemmGroupDev))   # (a device address: typed as the header's parameter)
 
     def launch():
         if fused:   # (the AdamDesc is held by this closure until the call)
-            call("asrx_gemm_grouped_xcd_adam", ctypes.byref(common), base, tg, bt, len(items), start,
+            call("asrx_gemm_grouped_xcd_adam", ctypes.byref(common), groups, tg, bt, len(items), start,
                  len(block_tile), ctypes.byref(adam), stream())
         else:
-            call("asrx_gemm_grouped_xcd", ctypes.byref(common), base, tg, bt, len(items), start,
+            call("asrx_gemm_grouped_xcd", ctypes.byref(common), groups, tg, bt, len(items), start,
                  len(block_tile), stream())
     return flops, launch, (dev, part), (queue, fused)
 
@@ -706,7 +710,7 @@ def cast(src, dst):
     call("asrx_cast", code(src), src.data_ptr(), code(dst), dst.data_ptr(), src.numel(), stream())
 
 
-EW_RELU_GRAD, EW_DROPOUT, EW_ADD = 0, 1, 2
+EW_RELU_GRAD, EW_DROPOUT, EW_ADD = (CONSTS["ASRX_EW_" + n] for n in ("RELU_GRAD", "DROPOUT", "ADD"))
 
 
 def ewise(op, a, out, b=None, p=0.0, seed=0):
@@ -728,11 +732,9 @@ def greedy_argmax(logits, V, tok_col, cur=None):
          tok_col.stride(0), _p(cur), stream())
 
 
-def beam_step(logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur=None, n_live=None):
-    """One beam-selection step (asrx_beam_step): logits fp32 [B*W, ld]; state_* = (score fp32, fin uint8, len int32),
-    each [B*W], two distinct sets; tok int64 / parent int32 / src_row int32 [B*W] take the chosen slots, cur (int64
-    [B*W], optional) the next step's tokens; n_live (int32 [1], optional, zero on entry) gains the count of
-    unfinished slots."""
+def _beam_step(name, scores, logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur, n_live):
+    """The checks and the call that asrx_beam_step and asrx_beam_step_joint share: their arguments differ only in
+    `scores`, which follows (logits, B, W, V, ld)."""
     (si, fi, li), (so, fo, lo) = state_in, state_out
     _cuda(logits, si, fi, li, so, fo, lo, tok, parent, src_row, cur, n_live)
     R = B * W
@@ -742,29 +744,34 @@ def beam_step(logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, c
                   (cur, torch.int64)):
         assert a is None or (a.dtype == dt and a.numel() == R and a.is_contiguous())
     assert n_live is None or (n_live.dtype == torch.int32 and n_live.numel() == 1)
-    call("asrx_beam_step", logits.data_ptr(), B, W, V, logits.stride(0), si.data_ptr(), fi.data_ptr(), li.data_ptr(),
+    call(name, logits.data_ptr(), B, W, V, logits.stride(0), *scores, si.data_ptr(), fi.data_ptr(), li.data_ptr(),
          int(eos), so.data_ptr(), tok.data_ptr(), _p(cur), parent.data_ptr(), src_row.data_ptr(), fo.data_ptr(),
          lo.data_ptr(), _p(n_live), stream())
+
+
+def beam_step(logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur=None, n_live=None):
+    """One beam-selection step (asrx_beam_step): logits fp32 [B*W, ld]; state_* = (score fp32, fin uint8, len int32),
+    each [B*W], two distinct sets; tok int64 / parent int32 / src_row int32 [B*W] take the chosen slots, cur (int64
+    [B*W], optional) the next step's tokens; n_live (int32 [1], optional, zero on entry) gains the count of
+    unfinished slots."""
+    _beam_step("asrx_beam_step", (), logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur, n_live)
 
 
 def beam_step_joint(logits, V, B, W, eos, extra, att_weight, extra_weight, state_in, state_out, tok, parent, src_row,
                     cur=None, n_live=None):
     """beam_step with a second score per candidate (asrx_beam_step_joint): a live beam's candidate is score +
     att_weight * log_softmax(logits)[v] + extra_weight * extra[w][v]; extra fp32 [B*W, ld_extra]."""
-    (si, fi, li), (so, fo, lo) = state_in, state_out
-    _cuda(logits, extra, si, fi, li, so, fo, lo, tok, parent, src_row, cur, n_live)
-    R = B * W
-    assert logits.dtype == torch.float32 and logits.shape[0] == R and logits.stride(1) == 1
-    assert extra.dtype == torch.float32 and extra.shape[0] == R and extra.stride(1) == 1 and extra.shape[1] >= V
-    for a, dt in ((si, torch.float32), (so, torch.float32), (fi, torch.uint8), (fo, torch.uint8), (li, torch.int32),
-                  (lo, torch.int32), (tok, torch.int64), (parent, torch.int32), (src_row, torch.int32),
-                  (cur, torch.int64)):
-        assert a is None or (a.dtype == dt and a.numel() == R and a.is_contiguous())
-    assert n_live is None or (n_live.dtype == torch.int32 and n_live.numel() == 1)
-    call("asrx_beam_step_joint", logits.data_ptr(), B, W, V, logits.stride(0), extra.data_ptr(), extra.stride(0),
-         float(att_weight), float(extra_weight), si.data_ptr(), fi.data_ptr(), li.data_ptr(), int(eos), so.data_ptr(),
-         tok.data_ptr(), _p(cur), parent.data_ptr(), src_row.data_ptr(), fo.data_ptr(), lo.data_ptr(), _p(n_live),
-         stream())
+    _cuda(extra)
+    assert extra.dtype == torch.float32 and extra.shape[0] == B * W and extra.stride(1) == 1 and extra.shape[1] >= V
+    _beam_step("asrx_beam_step_joint", (extra.data_ptr(), extra.stride(0), float(att_weight), float(extra_weight)),
+               logits, V, B, W, eos, state_in, state_out, tok, parent, src_row, cur, n_live)
+
+
+def _selection(B, W, parent, tok, fin_prev):
+    """The check CtcPrefix.advance and NgramState.advance share: parent int32, tok int64, fin_prev uint8, [B*W]."""
+    _cuda(parent, tok, fin_prev)
+    for a, dt in ((parent, torch.int32), (tok, torch.int64), (fin_prev, torch.uint8)):
+        assert a.dtype == dt and a.numel() == B * W and a.is_contiguous()
 
 
 class CtcPrefix:
@@ -803,10 +810,7 @@ class CtcPrefix:
     def advance(self, eos, parent, tok, fin_prev):
         """The chosen slots' states from their parents' (parent int32 / tok int64 [B*W] of the selection, fin_prev
         uint8 [B*W] its input flags)."""
-        _cuda(parent, tok, fin_prev)
-        R = self.B * self.W
-        for a, dt in ((parent, torch.int32), (tok, torch.int64), (fin_prev, torch.uint8)):
-            assert a.dtype == dt and a.numel() == R and a.is_contiguous()
+        _selection(self.B, self.W, parent, tok, fin_prev)
         (si, pi, li), (so, po, lo) = self.cur, self.alt
         call("asrx_ctc_prefix_advance", self.logp.data_ptr(), self.frames.data_ptr(), self.B, self.W, self.T, self.V,
              self.blank, int(eos), parent.data_ptr(), tok.data_ptr(), fin_prev.data_ptr(), si.data_ptr(),
@@ -814,7 +818,7 @@ class CtcPrefix:
         self.cur, self.alt = self.alt, self.cur
 
 
-NGRAM_LDS_V = 8192   # ASRX_NGRAM_LDS_V: asrx_ngram_score builds rows of up to this many columns in LDS
+NGRAM_LDS_V = CONSTS["ASRX_NGRAM_LDS_V"]   # asrx_ngram_score builds rows of up to this many columns in LDS
 
 
 def _ngram_table(lm, *ts):
@@ -851,10 +855,7 @@ class NgramState:
 
     def advance(self, eos, parent, tok, fin_prev):
         """The chosen slots' contexts from their parents' (the arguments of CtcPrefix.advance)."""
-        _cuda(parent, tok, fin_prev)
-        R = self.B * self.W
-        for a, dt in ((parent, torch.int32), (tok, torch.int64), (fin_prev, torch.uint8)):
-            assert a.dtype == dt and a.numel() == R and a.is_contiguous()
+        _selection(self.B, self.W, parent, tok, fin_prev)
         call("asrx_ngram_advance", *self.table, self.B, self.W, int(eos), parent.data_ptr(), tok.data_ptr(),
              fin_prev.data_ptr(), self.cur.data_ptr(), self.alt.data_ptr(), stream())
         self.cur, self.alt = self.alt, self.cur
@@ -984,6 +985,11 @@ def _lengths(lengths, B):
     return _p(lengths)
 
 
+def _stats(mean, istd, n):   # the CMVN statistics: fp32 [n] each, or None
+    for v in (mean, istd):
+        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n)
+
+
 def logmel(audio, basis, fb, fb_range, out, ws, *, n_fft, hop, power=2, scale=1.0, wave_lengths=None, log_mode=0,
            log_mul=1.0, log_eps=1e-6, mean=None, istd=None, pad_value=0.0, frame_lengths=None):
     """out (B, n_mels, frames) = the (log-)mel features of fp32 audio (B, samples) in one call (asrx_logmel, DESIGN.md
@@ -1000,13 +1006,10 @@ def logmel(audio, basis, fb, fb_range, out, ws, *, n_fft, hop, power=2, scale=1.
     assert basis.dtype == torch.float32 and basis.is_contiguous() and tuple(basis.shape) == (2 * nbins, n_fft)
     frames = (S - n_fft) // hop + 1 if S >= n_fft else 0
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, n_mels, frames)
-    for v in (mean, istd):
-        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n_mels)
-    if frame_lengths is not None:
-        assert frame_lengths.dtype == torch.int32 and frame_lengths.is_contiguous() and frame_lengths.numel() == B
+    _stats(mean, istd, n_mels)
     call("asrx_logmel", audio.data_ptr(), B, S, audio.stride(0), _lengths(wave_lengths, B), basis.data_ptr(), n_fft,
          hop, nbins, power, scale, fb.data_ptr(), fb_range.data_ptr(), n_mels, log_mode, log_mul, log_eps, _p(mean),
-         _p(istd), pad_value, ws.data_ptr(), ws.numel(), out.data_ptr(), _p(frame_lengths), stream())
+         _p(istd), pad_value, ws.data_ptr(), ws.numel(), out.data_ptr(), _lengths(frame_lengths, B), stream())
 
 
 def logmel_pass(ws, fb, fb_range, out, *, n_fft, hop, power=2, scale=1.0, wave_lengths=None, log_mode=0, log_mul=1.0,
@@ -1020,13 +1023,10 @@ def logmel_pass(ws, fb, fb_range, out, *, n_fft, hop, power=2, scale=1.0, wave_l
     assert fb.dtype == torch.float32 and fb.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous()
     assert out.shape[1] == n_mels and not fb_range.is_cuda and fb_range.dtype == torch.int32
     assert fb_range.is_contiguous() and tuple(fb_range.shape) == (n_mels, 2)
-    for v in (mean, istd):
-        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n_mels)
-    if frame_lengths is not None:
-        assert frame_lengths.dtype == torch.int32 and frame_lengths.is_contiguous() and frame_lengths.numel() == B
+    _stats(mean, istd, n_mels)
     call("asrx_logmel_pass", ws.data_ptr(), B, frames, _lengths(wave_lengths, B), n_fft, hop, nbins, power, scale,
          fb.data_ptr(), fb_range.data_ptr(), n_mels, log_mode, log_mul, log_eps, _p(mean), _p(istd), pad_value,
-         out.data_ptr(), _p(frame_lengths), stream())
+         out.data_ptr(), _lengths(frame_lengths, B), stream())
 
 
 def stft_power(ws, out, *, power=2, scale=1.0):
@@ -1047,8 +1047,7 @@ def cmvn(x, out, *, lengths=None, mean=None, istd=None, norm_var=True, eps=1e-5,
     Bo, Fo, To, ob = _feat3(out, "out")
     if (B, F, T) != (Bo, Fo, To):
         raise ValueError(f"asrx: cmvn shapes differ: {tuple(x.shape)} vs {tuple(out.shape)}")
-    for v in (mean, istd):
-        assert v is None or (v.dtype == torch.float32 and v.is_contiguous() and v.numel() == F)
+    _stats(mean, istd, F)
     if B * F * T == 0:
         return
     call("asrx_cmvn", x.data_ptr(), out.data_ptr(), B, F, T, xb, ob, _lengths(lengths, B), _p(mean), _p(istd),
@@ -1186,7 +1185,7 @@ def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_gra
     return loss, dl, am
 
 
-CTC_REDUCTIONS = {"sum": 0, "mean": 1}   # ASRX_CTC_SUM, ASRX_CTC_MEAN
+CTC_REDUCTIONS = {"sum": CTC_SUM, "mean": CTC_MEAN}
 
 
 def ctc_workspace_elems(B, T, max_target_len):
@@ -1368,7 +1367,7 @@ def rescore_rank(att, ctc, B, W, att_weight, ctc_weight):
     return score, order
 
 
-ED_MODES = {"pairs": 0, "group": 1, "cross": 2}    # ASRX_ED_PAIRS / GROUP / CROSS
+ED_MODES = {"pairs": ED_PAIRS, "group": ED_GROUP, "cross": ED_CROSS}
 
 
 def _ctc_logits(logits, T, input_lengths, who=None):   # -> B of logits fp32 [B*T, ld], input_lengths int32 [B] or None
@@ -1501,7 +1500,7 @@ def adam_hyper(hyp, lr, beta1, beta2, step):
     upload(hyp, np.array([lr, 1.0 - beta1 ** step, 1.0 - beta2 ** step], dtype=np.float32))
 
 
-TUNE_KEYS = {"softmax_u": 1, "ln_rw": 2, "ln_pf": 3, "ln_bpc": 4}
+TUNE_KEYS = {k: CONSTS["ASRX_TUNE_" + k.upper()] for k in ("softmax_u", "ln_rw", "ln_pf", "ln_bpc")}
 
 
 def set_tuning(name, value):

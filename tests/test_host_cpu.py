@@ -19,7 +19,7 @@ def _declared_symbols():
     return sorted(set(re.findall(r"\b(?:int|int64_t)\s+(asrx_\w+)\s*\(", src)))
 
 
-# entry points with a non-int result, bound separately in asrx._lib.lib()
+# the attention size helpers (int64 result); SIGNATURES, derived from the header, holds them like every other entry
 _NON_INT = {"asrx_attn_dropmask_words", "asrx_attn_dq_acc_elems"}
 
 
@@ -76,6 +76,175 @@ def test_ctypes_struct_sizes_match_the_library():
     assert list(out) == [ctypes.sizeof(GemmDesc), ctypes.sizeof(AttnDesc), ctypes.sizeof(GemmGroupDev),
                          ctypes.sizeof(RowsumGroup), ctypes.sizeof(AdamDesc)]
     assert ctypes.sizeof(GemmGroupDev) == 64
+
+
+def test_ctypes_struct_fields_match_the_header():
+    """The descriptor structs field for field (names, order, types): the size test above passes two swapped fields of
+    equal width, and kernels.gemm fills GemmDesc with one positional constructor call.  The lists are written out, as
+    the hand-written binding had them; every pointer field is a c_void_p."""
+    import ctypes
+    import asrx
+    from asrx._lib import AdamDesc, AttnDesc, GemmDesc, GemmGroupDev, RowsumGroup
+    i32, i64, u64, f32, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_void_p
+    assert GemmDesc._fields_ == [
+        ("m", i32), ("n", i32), ("k", i32),
+        ("in_dtype", i32),
+        ("a", vp), ("lda", i64), ("a_trans", i32),
+        ("b", vp), ("ldb", i64), ("b_trans", i32),
+        ("c", vp), ("ldc", i64), ("c_dtype", i32),
+        ("batch", i32), ("batch_inner", i32),
+        ("sa_outer", i64), ("sa_inner", i64), ("sb_outer", i64), ("sb_inner", i64),
+        ("sc_outer", i64), ("sc_inner", i64),
+        ("alpha", f32), ("beta", f32),
+        ("bias", vp),
+        ("rowadd", vp), ("ld_rowadd", i64), ("rowadd_mod", i32),
+        ("relu", i32),
+        ("dropout_p", f32), ("seed", u64),
+        ("gate", vp), ("ld_gate", i64), ("gate_dtype", i32),
+        ("resid", vp), ("ld_resid", i64), ("resid_dtype", i32),
+        ("splitk", i32), ("workspace", vp), ("workspace_elems", i64),
+        ("tile", i32),
+        ("rowsum_a", vp), ("rowsum_ws", vp),
+        ("mask_out", vp), ("ld_mask", i64),
+        ("kernel", i32),
+    ]
+    assert AttnDesc._fields_ == [
+        ("batch", i32), ("heads", i32), ("lq", i32), ("lk", i32), ("dh", i32),
+        ("q", vp), ("q_rstride", i64), ("q_bstride", i64),
+        ("k", vp), ("k_rstride", i64), ("k_bstride", i64),
+        ("v", vp), ("v_rstride", i64), ("v_bstride", i64),
+        ("o", vp), ("o_rstride", i64), ("o_bstride", i64),
+        ("lse", vp),
+        ("scale", f32),
+        ("mask_mode", i32), ("causal", i32),
+        ("kvalid", vp), ("qvalid", vp), ("valid_bstride", i64),
+        ("mask", vp), ("mask_sb", i64), ("mask_sq", i64), ("mask_sk", i64),
+        ("dropout_p", f32), ("seed", u64),
+        ("dout", vp), ("do_rstride", i64), ("do_bstride", i64),
+        ("dq", vp), ("dq_rstride", i64), ("dq_bstride", i64),
+        ("dk", vp), ("dk_rstride", i64), ("dk_bstride", i64),
+        ("dv", vp), ("dv_rstride", i64), ("dv_bstride", i64),
+        ("delta", vp), ("dq_acc", vp),
+        ("dropmask", vp), ("dropmask_ready", i32),
+        ("o_lo", vp),
+    ]
+    assert [n for n, _ in RowsumGroup._fields_] == ["in_", "rows", "cols", "out", "accumulate"]   # `in` is a keyword
+    structs = [GemmDesc, AttnDesc, GemmGroupDev, RowsumGroup, AdamDesc]
+    assert [c.__name__ for c in structs] == ["GemmDesc", "AttnDesc", "GemmGroupDev", "RowsumGroup", "AdamDesc"]
+    out = (ctypes.c_int64 * 5)()
+    assert asrx.native().asrx_struct_sizes(out, 5) == 5
+    assert list(out) == [ctypes.sizeof(c) for c in structs]
+
+
+def _header_text():
+    """include/asrx.h without its comments."""
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(REPO, "include", "asrx.h")).read(), flags=re.S)
+
+
+def test_signature_matches_the_header():
+    """Every prototype of the header against the binding: one argtype per parameter, of the parameter's kind, and the
+    restype.  The header is read again here, by this test's own rule (split on commas, `*` means pointer), not by
+    asrx._lib's parser: a second, independent reading."""
+    import ctypes
+    import asrx
+    from asrx import _lib
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+               "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
+    structs = {"asrx_gemm_desc": _lib.GemmDesc, "asrx_attn_desc": _lib.AttnDesc, "asrx_adam_desc": _lib.AdamDesc,
+               "asrx_gemm_group_dev": _lib.GemmGroupDev, "asrx_rowsum_group": _lib.RowsumGroup}
+    protos = re.findall(r"\b(int|int64_t)\s+(asrx_\w+)\s*\((.*?)\)\s*;", _header_text(), re.S)
+    assert [name for _, name, _ in protos] and sorted(name for _, name, _ in protos) == _declared_symbols()
+    assert set(_lib.SIGNATURES) == set(_lib.RESTYPES) == {name for _, name, _ in protos}
+    lib = asrx.native()
+    for ret, name, params in protos:
+        kinds = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = p.replace("*", " * ").split()
+            words = [w for w in words if w != "const"]
+            if "*" not in words:
+                assert len(words) == 2, (name, p)
+                kinds.append(scalars[words[0]])
+            elif words[0] == "char":
+                kinds.append(ctypes.c_char_p)
+            elif words[0] in structs:
+                kinds.append(ctypes.POINTER(structs[words[0]]))
+            else:
+                assert not words[0].startswith("asrx_"), (name, p)
+                kinds.append(ctypes.c_void_p)
+        assert _lib.SIGNATURES[name] == kinds, name
+        assert _lib.RESTYPES[name] is scalars[ret], name
+        fn = getattr(lib, name)
+        assert list(fn.argtypes) == kinds and fn.restype is scalars[ret], name
+
+
+def test_signatures_written_out():
+    """A few entries in full, as the hand-written table had them (its c_void_p for the asrx_gemm_group_dev* parameter
+    now the struct's pointer type): together they hold every kind of type the binding knows."""
+    import ctypes
+    from asrx._lib import AdamDesc, GemmDesc, GemmGroupDev, RESTYPES, SIGNATURES
+    c_i32, c_i64, c_u64, c_f32, c_vp = (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                        ctypes.c_void_p)
+    assert SIGNATURES["asrx_version"] == []
+    assert SIGNATURES["asrx_gemm_kernel_name"] == [ctypes.POINTER(GemmDesc), ctypes.c_char_p, c_i32]
+    assert SIGNATURES["asrx_gemm_grouped_xcd_adam"] == [
+        ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmGroupDev), c_vp, c_vp, c_i32, c_i32, c_i32,
+        ctypes.POINTER(AdamDesc), c_vp]
+    assert SIGNATURES["asrx_specaug"] == [
+        c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32,
+        c_f32, c_u64, c_u64, c_vp, c_vp]
+    assert SIGNATURES["asrx_logmel"] == [
+        c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_i32, c_i32,
+        c_f32, c_f32, c_vp, c_vp, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp]
+    assert len(SIGNATURES["asrx_logmel"]) == 25
+    assert SIGNATURES["asrx_ctc_workspace_elems"] == [c_i32, c_i32, c_i32]
+    assert SIGNATURES["asrx_attn_dropmask_words"] == [c_i32, c_i32, c_i32, c_i32]
+    assert RESTYPES["asrx_ctc_workspace_elems"] is c_i64 and RESTYPES["asrx_attn_dropmask_words"] is c_i64
+    assert RESTYPES["asrx_version"] is RESTYPES["asrx_logmel"] is ctypes.c_int
+    assert {n for n, t in RESTYPES.items() if t is not ctypes.c_int} == {
+        "asrx_ctc_workspace_elems", "asrx_ctc_align_workspace_words", "asrx_attn_dropmask_words",
+        "asrx_attn_dq_acc_elems"}
+
+
+def test_constants_mirror_the_header_defines():
+    """Every Python name that stands for an ASRX_* define of the header has the value it had when it was written by
+    hand."""
+    from asrx import _lib, kernels as K
+    assert (_lib.BF16, _lib.F32, _lib.BITS) == (0, 1, 2)
+    assert (_lib.CTC_SUM, _lib.CTC_MEAN) == (0, 1)
+    assert (_lib.ED_PAIRS, _lib.ED_GROUP, _lib.ED_CROSS) == (0, 1, 2)
+    assert (_lib.NGRAM_MAX_ORDER, _lib.SPECAUG_MAX_MASKS, _lib.SPECAUG_RUN, _lib.LOGMEL_MAX_MELS) == (6, 8, 1024, 256)
+    assert _lib.ERRORS == {-1: "bad argument", -2: "launch failure", -3: "unsupported shape/layout"}
+    assert (_lib.CTC_MAX_TARGET, _lib.MAX_ROWSUM_GROUPS) == (255, 64)        # (no define: literals in asrx._lib)
+    assert K.KERNEL_CODES == {"auto": 0, "p3": 1, "reg": 3, "ring": 4, "ring128": 5, "p4": 6, "ws": 8, "ws64": 10}
+    assert K._TILE_CODE == {"p3": ((256, 128), 3), "p4": ((256, 256), 4), "ws": ((256, 128), 5),
+                            "reg": ((128, 128), 128)}
+    assert K.NGRAM_LDS_V == 8192
+    assert (K.EW_RELU_GRAD, K.EW_DROPOUT, K.EW_ADD) == (0, 1, 2)
+    assert K.CTC_REDUCTIONS == {"sum": 0, "mean": 1}
+    assert K.ED_MODES == {"pairs": 0, "group": 1, "cross": 2}
+    assert K.TUNE_KEYS == {"softmax_u": 1, "ln_rw": 2, "ln_pf": 3, "ln_bpc": 4}
+    assert (K.ROW_SCALE, K.ROW_ADD, K.CONV_BWD_MAXLDS) == (0, 1, 80 * 1024)  # (no define: literals in asrx.kernels)
+    assert all(type(v) is int for v in _lib.CONSTS.values()) and _lib.CONSTS["ASRX_OK"] == 0
+
+
+def test_a_missing_or_unknown_header_is_an_error(tmp_path):
+    """No fallback table: without the header the binding raises and names the path; a type the parser does not know
+    is an error too, not a guess."""
+    from asrx._lib import _parse_header
+    missing = str(tmp_path / "asrx.h")
+    with pytest.raises(RuntimeError, match=re.escape(missing)):
+        _parse_header(missing)
+    (tmp_path / "asrx.h").write_text("int asrx_new_thing(const double x, void* stream);\n")
+    with pytest.raises(RuntimeError, match="const double x"):
+        _parse_header(missing)
+    (tmp_path / "asrx.h").write_text("float asrx_new_thing(float x, void* stream);\n")
+    with pytest.raises(RuntimeError, match="asrx_new_thing"):
+        _parse_header(missing)
+    (tmp_path / "asrx.h").write_text("#define ASRX_K (-7)\nint64_t asrx_new_thing(const double* x, void* stream);\n")
+    structs, sigs, res, consts = _parse_header(missing)
+    import ctypes
+    assert (structs, consts) == ({}, {"ASRX_K": -7})
+    assert sigs == {"asrx_new_thing": [ctypes.c_void_p, ctypes.c_void_p]} and res["asrx_new_thing"] is ctypes.c_int64
 
 
 def test_abi_upload_and_seed_offset_validate_arguments_without_gpu():
