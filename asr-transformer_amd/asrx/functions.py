@@ -124,7 +124,32 @@ def encoder_input(C, x):
     return buf.reshape(B * T2, F2 * Cc), B, T2
 
 
-def encoder_fwd(C, enc, feats, B, T):
+def key_spec(lengths, B, T, dev, subsample=0):
+    """Padded batches: (rows int32 [B], MaskSpec.keys(valid [B, T])) of per-utterance lengths, one
+    asrx_length_mask launch; (None, None) without lengths.  subsample = 0: the lengths count the T rows themselves
+    (encoder frames); 2: spectrogram frames in front of the two k3/s2 convolutions."""
+    if lengths is None:
+        return None, None
+    lengths = torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if lengths.numel() != B:
+        raise ValueError(f"asrx: {lengths.numel()} lengths for a batch of {B}")
+    rows, valid = K.length_mask(lengths, T, subsample)
+    return rows, MaskSpec.keys(valid)
+
+
+def pad_lengths(model, input_lengths, dev=None):
+    """The lengths a Transformer entry point masks its attention with: input_lengths where the model was built (or
+    set) with mask_padding, else None — the call then runs launch for launch as without the feature.  dev: return
+    them as the int32 vector on that device that key_spec hands to the kernel (the Trainer's static graph input)."""
+    if input_lengths is None or not getattr(model, "mask_padding", False):
+        return None
+    if dev is None:
+        return input_lengths
+    return torch.as_tensor(input_lengths).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+
+
+def encoder_fwd(C, enc, feats, B, T, spec=None):
+    """spec: MaskSpec.keys over the T rows of each utterance, for every layer's self-attention (None: no mask)."""
     d = enc.emb_dim
     H = enc.num_heads
     x = torch.empty(B * T, d, dtype=torch.float32, device=feats.device)
@@ -134,7 +159,7 @@ def encoder_fwd(C, enc, feats, B, T):
     K.linear(feats, C.W(enc._lin_in.weight), x, bias=enc._lin_in.bias.data, rowadd=pe, rowadd_mod=T, ld_rowadd=d)
     Ss = []
     for layer in enc._layers:
-        x, S = Bk.enc_layer_fwd(C, x, layer, B, T, H)
+        x, S = Bk.enc_layer_fwd(C, x, layer, B, T, H, spec)
         Ss.append(S)
     y, mean, rstd = Bk.ln_fwd(C, x, enc._norm_out)
     return y, dict(feats=feats, x=x, mean=mean, rstd=rstd, layers=Ss)
@@ -268,10 +293,11 @@ def _kv_block(C, dec):
     return W.view(n * 2 * d, d), bias, gW.view(n * 2 * d, d), gb
 
 
-def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None, group=1):
+def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None, group=1, xspec=None):
     """Decoder.forward as one native program over B token rows of length L.  group > 1 (eval only): every `group`
     consecutive rows decode against ONE encoder output, enc_c [(B / group) * Te, d]: self-attention runs as batch B,
-    cross-attention as batch B / group with group * L queries over the once-projected K/V (blocks.cross_attn_fwd)."""
+    cross-attention as batch B / group with group * L queries over the once-projected K/V (blocks.cross_attn_fwd).
+    xspec: MaskSpec.keys over the Te rows of each encoder output, for every layer's cross-attention (None: no mask)."""
     d, H, n = dec.emb_dim, dec.num_heads, len(dec._layers)
     dev = enc_c.device
     Md = B * L
@@ -289,7 +315,7 @@ def decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, final_norm=True, spec=None,
     K.linear(enc_c, Wkv, kv, bias=bkv)
     Ss = []
     for l, layer in enumerate(dec._layers):
-        x, S = Bk.dec_layer_fwd(C, x, layer, B, L, H, spec, kv[:, l * 2 * d:], n * 2 * d, Te, group)
+        x, S = Bk.dec_layer_fwd(C, x, layer, B, L, H, spec, kv[:, l * 2 * d:], n * 2 * d, Te, group, xspec)
         Ss.append(S)
     cls = dec._classifier
     if final_norm:
@@ -338,18 +364,19 @@ def ctc_head_fwd(C, model, enc_c):
     return logits
 
 
-def model_forward(C, model, spectrum, text, mask, spec=None, ctc=False):
+def model_forward(C, model, spectrum, text, mask, spec=None, ctc=False, enc_spec=None):
     """Transformer.forward (model.py:194-198) as one native program. Returns (logits [B*L, Vp] fp32, S).  spec:
     the decoder's self-attention mask when the caller already built it (mask is then unused).  ctc: also run the CTC
-    head on the encoder output, S["ctc_logits"] (fp32 [B*T', Vp])."""
+    head on the encoder output, S["ctc_logits"] (fp32 [B*T', Vp]).  enc_spec: MaskSpec.keys over the T' encoder rows
+    of each utterance; it masks the encoder's self-attention and the decoder's cross-attention."""
     dev = C.store.device
     spectrum = spectrum.to(dev)
     feats, Sf = Bk.frontend_fwd(C, spectrum, model.input_layer[0], model.input_layer[2])
     B = spectrum.shape[0]
     T2 = Sf["dims"][-1]
-    enc, Se = encoder_fwd(C, model.encoder, feats, B, T2)
+    enc, Se = encoder_fwd(C, model.encoder, feats, B, T2, enc_spec)
     L = text.shape[1]
-    logits, Sd = decoder_fwd(C, model.decoder, text, mask, enc, B, L, T2, spec=spec)
+    logits, Sd = decoder_fwd(C, model.decoder, text, mask, enc, B, L, T2, spec=spec, xspec=enc_spec)
     S = dict(f=Sf, e=Se, d=Sd)
     if ctc:
         S["ctc_logits"] = ctc_head_fwd(C, model, enc)
@@ -399,8 +426,8 @@ def _dlogits_padded(C, dlogits, rows, V, Vp):
 
 class _TransformerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, C, spectrum, text, mask, *params):
-        logits, S = model_forward(C, model, spectrum, text, mask)
+    def forward(ctx, model, C, spectrum, text, mask, enc_spec, *params):
+        logits, S = model_forward(C, model, spectrum, text, mask, enc_spec=enc_spec)
         ctx.model, ctx.C, ctx.S = model, C, S
         B, L = text.shape
         V = model.decoder._classifier.V
@@ -414,12 +441,18 @@ class _TransformerFn(torch.autograd.Function):
         C = ctx.C
         model_backward(C, ctx.model, ctx.S, _dlogits_padded(C, dlogits, B * L, V, Vp))
         ctx.S = None
-        return (None,) * (5 + len(_params(ctx.model)))
+        return (None,) * (6 + len(_params(ctx.model)))
 
 
-def transformer(model, spectrum, text, mask):
+def transformer(model, spectrum, text, mask, input_lengths=None):
+    """input_lengths (valid encoder frames per utterance) mask the padded frames where the model has mask_padding."""
     C = make_ctx(model, model.decoder.p)
-    return _TransformerFn.apply(model, C, spectrum, text, mask, *_params(model))
+    enc_spec = None
+    lens = pad_lengths(model, input_lengths)
+    if lens is not None:
+        from .model import subsampled
+        _, enc_spec = key_spec(lens, spectrum.shape[0], subsampled(spectrum.shape[-1]), C.store.device)
+    return _TransformerFn.apply(model, C, spectrum, text, mask, enc_spec, *_params(model))
 
 
 class _FrontEndFn(torch.autograd.Function):
@@ -449,9 +482,9 @@ def frontend(fe, spectrum):
 
 class _EncoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, enc, C, x, *params):
+    def forward(ctx, enc, C, x, input_lengths, *params):
         feats, B, T = encoder_input(C, x)
-        y, S = encoder_fwd(C, enc, feats, B, T)
+        y, S = encoder_fwd(C, enc, feats, B, T, key_spec(input_lengths, B, T, feats.device)[1])
         ctx.enc, ctx.C, ctx.S, ctx.xshape = enc, C, S, (B, T, x.shape[1], x.shape[2])
         return y.view(B, T, -1)
 
@@ -465,21 +498,22 @@ class _EncoderFn(torch.autograd.Function):
         if own:
             C.flush_wgrad()
         dx = dfeats.view(B, T, F2, Cc).permute(0, 3, 2, 1)
-        return (None, None, dx) + (None,) * len(_params(ctx.enc))
+        return (None, None, dx, None) + (None,) * len(_params(ctx.enc))
 
 
-def encoder(enc, x):
+def encoder(enc, x, input_lengths=None):
     C = make_ctx(enc, enc.p)
-    return _EncoderFn.apply(enc, C, x, *_params(enc))
+    return _EncoderFn.apply(enc, C, x, input_lengths, *_params(enc))
 
 
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, dec, C, text, mask, enc_x, *params):
+    def forward(ctx, dec, C, text, mask, enc_x, enc_lengths, *params):
         B, Te, d = enc_x.shape
         enc_c = enc_x.reshape(B * Te, d).to(C.cd).contiguous()
         L = text.shape[1]
-        logits, S = decoder_fwd(C, dec, text, mask, enc_c, B, L, Te)
+        xspec = key_spec(enc_lengths, B, Te, enc_c.device)[1]
+        logits, S = decoder_fwd(C, dec, text, mask, enc_c, B, L, Te, xspec=xspec)
         ctx.dec, ctx.C, ctx.S = dec, C, S
         V = dec._classifier.V
         ctx.shape = (B, L, V, logits.shape[1], Te, d)
@@ -495,16 +529,16 @@ class _DecoderFn(torch.autograd.Function):
         denc = decoder_bwd(C, ctx.dec, ctx.S, _dlogits_padded(C, dlogits, B * L, V, Vp))
         if own:
             C.flush_wgrad()
-        return (None, None, None, None, denc.view(B, Te, d)) + (None,) * len(_params(ctx.dec))
+        return (None, None, None, None, denc.view(B, Te, d), None) + (None,) * len(_params(ctx.dec))
 
 
-def decoder(dec, x, mask, enc_x):
+def decoder(dec, x, mask, enc_x, enc_lengths=None):
     C = make_ctx(dec, dec.p)
-    return _DecoderFn.apply(dec, C, x, mask, enc_x, *_params(dec))
+    return _DecoderFn.apply(dec, C, x, mask, enc_x, enc_lengths, *_params(dec))
 
 
 @torch.no_grad()
-def decoder_evaluate(dec, x, enc_x):
+def decoder_evaluate(dec, x, enc_x, enc_lengths=None):
     """Decoder.evaluate (model.py:125-151) with its quirks: causal-only mask, NO final LayerNorm before the
     classifier, no break on EOS (every sample runs seq_len steps), returns the LAST sample's token row and the list
     of logits snapshots `prob[:, :-1].squeeze()` (one per EOS hit or final step, samples in order).
@@ -513,15 +547,18 @@ def decoder_evaluate(dec, x, enc_x):
     the reference's full-prefix recomputation redundant), the cross-attention K/V of all layers projected once, and
     the next tokens chosen on the GPU (asrx_greedy_argmax) — no host round trip until the end.  Train mode with
     dropout (model.py:137 applies self._dropout, and every layer's dropouts are live): the reference's
-    per-sample prefix recomputation, whose fresh masks a cache cannot reproduce."""
+    per-sample prefix recomputation, whose fresh masks a cache cannot reproduce.
+
+    enc_lengths (valid rows of each encoder output): the cross-attention masks the padded rows."""
     if dec.training and dec.p > 0:
-        return _decoder_evaluate_recompute(dec, x, enc_x)
-    return _decoder_evaluate_cached(dec, x, enc_x)
+        return _decoder_evaluate_recompute(dec, x, enc_x, enc_lengths)
+    return _decoder_evaluate_cached(dec, x, enc_x, enc_lengths)
 
 
-def _decoder_evaluate_recompute(dec, x, enc_x):
+def _decoder_evaluate_recompute(dec, x, enc_x, enc_lengths=None):
     C = make_ctx(dec, dec.p)
     B, Te, d = enc_x.shape
+    xspec = key_spec(enc_lengths, B, Te, enc_x.device)[1]
     V = dec._classifier.V
     probs = []
     decoder_input = None
@@ -531,7 +568,8 @@ def _decoder_evaluate_recompute(dec, x, enc_x):
         for i in range(1, dec._seq_len + 1):
             L = decoder_input.shape[1]
             spec = MaskSpec(1, True)
-            logits, _ = decoder_fwd(C, dec, decoder_input, None, e, 1, L, Te, final_norm=False, spec=spec)
+            xs = None if xspec is None else MaskSpec.keys(xspec.kvalid[s:s + 1])
+            logits, _ = decoder_fwd(C, dec, decoder_input, None, e, 1, L, Te, final_norm=False, spec=spec, xspec=xs)
             prob = logits[:, :V].view(1, L, V)
             next_word = prob.argmax(dim=-1)[:, -1].unsqueeze(1)
             decoder_input = torch.cat([decoder_input, next_word.to(decoder_input.dtype)], dim=-1)
@@ -557,16 +595,17 @@ def _mha_fwd_w(C, m):
     return sum(((C.W(p)[r], b.data[r]) for p, b, r in _mha_params(m)), ())
 
 
-def _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te):
+def _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te, xspec=None):
     """One decoder position for B samples x W hypotheses (rows b*W + w): the embedding of `cur` at position t through
     every layer (pe = the positional table), returning the fp32 stream [B*W, d].  kvs [n][B*W][P][2d] are the
     self-attention K/V caches, which gain position t; kvx [B*Te][n*2d] holds every layer's cross-attention K/V per
     SAMPLE: the W hypotheses of a sample share it, so cross-attention runs as batch = B with W queries each (W = 1:
-    greedy decoding)."""
+    greedy decoding).  xspec: MaskSpec.keys over each sample's Te encoder rows, for the cross-attention."""
     d, H = dec.emb_dim, dec.num_heads
     dh = d // H
     R = B * W
     none = MaskSpec()
+    cross = xspec or none
     xs = torch.empty(R, d, dtype=torch.float32, device=cur.device)
     K.embed_fwd(cur, dec._embedding.weight.data, pe[t:t + 1], xs, 1)
     for l, layer in enumerate(dec._layers):
@@ -575,19 +614,20 @@ def _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te):
         h, _, _ = Bk.ln_fwd(C, xs, layer._norm1)
         x1, _ = Bk.attn_core_fwd(C, _mha_fwd_w(C, mha), h, R, H, dh, 1, t + 1, none, xk=h, kv=kvs[l],
                                  kv_dst=kvs[l][:, t], resid=xs)
-        # cross-attention over the encoder output (no mask, model.py:71)
+        # cross-attention over the encoder output (no mask, model.py:71, unless the batch is padded: xspec)
         h2, _, _ = Bk.ln_fwd(C, x1, layer._norm2)
         w = (C.W(cr.wq), cr.bq.data, None, None, C.W(cr._out_linear.weight), cr._out_linear.bias.data)
-        x2, _ = Bk.attn_core_fwd(C, w, h2, B, H, dh, W, Te, none, kv=kvx[:, l * 2 * d:], resid=x1)
+        x2, _ = Bk.attn_core_fwd(C, w, h2, B, H, dh, W, Te, cross, kv=kvx[:, l * 2 * d:], resid=x1)
         xs, _ = Bk.ffn_fwd(C, x2, layer._norm3, layer._feedforward)
     return xs
 
 
-def _decoder_evaluate_cached(dec, x, enc_x):
+def _decoder_evaluate_cached(dec, x, enc_x, enc_lengths=None):
     C = make_ctx(dec, 0.0)
     C.train, C.p = False, 0.0
     dev = enc_x.device
     B, Te, d = enc_x.shape
+    xspec = key_spec(enc_lengths, B, Te, dev)[1]
     n, H, steps = len(dec._layers), dec.num_heads, dec._seq_len
     dh = d // H
     cls = dec._classifier
@@ -610,7 +650,7 @@ def _decoder_evaluate_cached(dec, x, enc_x):
     tokens[:, :L0] = x.to(device=dev, dtype=torch.int64)
     cur = tokens[:, 0].contiguous()
     for t in range(P):
-        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, 1, Te)
+        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, 1, Te, xspec)
         hc = torch.empty(B, d, dtype=C.cd, device=dev)       # no final LayerNorm in evaluate (model.py:142)
         K.cast(xs, hc)
         lg = logits[:, t]
@@ -683,7 +723,7 @@ def check_lm(lm, lm_weight, token_bonus, V=None):
 
 @torch.no_grad()
 def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
-                        ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0):
+                        ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
     """Beam-search decoding on the KV-cached decoder (the reference has none: Decoder.evaluate, model.py:125-151, is
     greedy).  x (B, L0 >= 1) is the prompt, prefilled with teacher forcing; `max_len` new tokens (default seq_len)
     are then chosen with `beam` hypotheses per sample, each step keeping the `beam` best continuations by summed
@@ -711,7 +751,10 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
     scores (1 - lam) * log p_att + lam * log p_ctc + beta * log p_lm + token_bonus * len.  Two more launches per step:
     asrx_ngram_score writes the `extra` matrix of asrx_beam_step_joint (with lam > 0 it folds lam * the CTC scores in),
     asrx_ngram_advance moves the survivors' LM contexts.  The prompt must be one token, the LM's sentence start.
-    lm=None or lm_weight = 0 (default) issues exactly the launches described above."""
+    lm=None or lm_weight = 0 (default) issues exactly the launches described above.
+
+    enc_lengths (valid rows of each encoder output): every cross-attention masks the padded rows (one more launch in
+    front, asrx_length_mask).  None (default) issues exactly the launches described above."""
     lam = float(ctc_weight)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1]")
@@ -752,6 +795,7 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
         return BeamResult(prompt[:, None, :].expand(B, nbest, L0).contiguous(),
                           torch.zeros(B, nbest, dtype=torch.int64), torch.zeros(B, nbest, dtype=torch.float32))
     R = B * W
+    xspec = key_spec(enc_lengths, B, Te, dev)[1]
     enc_c = torch.empty(B * Te, d, dtype=C.cd, device=dev)
     K.cast(enc_x.reshape(B * Te, d).contiguous(), enc_c)
     Wkv, bkv, _, _ = _kv_block(C, dec)
@@ -783,7 +827,7 @@ def decoder_beam_search(dec, x, enc_x, beam=4, max_len=None, length_penalty=0.0,
         ngram = K.NgramState(lm, B, W)
         extra = torch.empty(R, Vp, dtype=torch.float32, device=dev)
     for t in range(P):
-        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te)
+        xs = _decode_position(C, dec, cur, pe, t, kvs, kvx, B, W, Te, xspec)
         s = t - (L0 - 1)
         if s < 0:
             cur = xr[:, t + 1].contiguous()
@@ -832,7 +876,8 @@ def transformer_beam_search(model, spectrum, text=None, ctc_weight=0.0, input_le
     """Transformer.beam_search: front end and encoder as in `evaluate` (model.py:201-206), then
     decoder_beam_search.  text=None starts every sample on a BOS column (id 1).  ctc_weight > 0: joint
     CTC/attention decoding, the one encoder output also feeding the model's CTC head (input_lengths: optional valid
-    encoder frames per sample)."""
+    encoder frames per sample; on a model with mask_padding they also mask the encoder's self-attention and the
+    cross-attention, with or without the CTC term)."""
     lam = float(ctc_weight)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1]")
@@ -843,10 +888,13 @@ def transformer_beam_search(model, spectrum, text=None, ctc_weight=0.0, input_le
     beta, _ = check_lm(kw.get("lm"), kw.get("lm_weight", 0.0), kw.get("token_bonus", 0.0), model.decoder._classifier.V)
     if beta > 0.0 and text is not None and text.dim() == 2 and text.shape[1] != 1:
         raise ValueError(f"lm_weight > 0 takes a one-token prompt, got L0 = {text.shape[1]}")
+    lens = pad_lengths(model, input_lengths)
     with torch.no_grad():
-        enc = model.encoder(model.input_layer(spectrum))
+        enc = _encode(model, spectrum, lens)
     if text is None:
         text = torch.ones(spectrum.shape[0], 1, dtype=torch.int64)
+    if lens is not None:
+        kw["enc_lengths"] = lens
     if lam == 0.0:
         return decoder_beam_search(model.decoder, text, enc, **kw)
     logits, B, T = _ctc_logits_of(model, enc)
@@ -854,20 +902,27 @@ def transformer_beam_search(model, spectrum, text=None, ctc_weight=0.0, input_le
                                ctc_weight=lam, **kw)
 
 
-@torch.no_grad()
-def transformer_evaluate(model, spectrum, text):
-    """Transformer.evaluate (model.py:201-206)."""
+def _encode(model, spectrum, lens=None):
+    """Front end and encoder as in `evaluate` (model.py:201-203); lens: the lengths to mask with (pad_lengths)."""
     feats = model.input_layer(spectrum)
-    enc = model.encoder(feats)
-    return model.decoder.evaluate(text, enc)
+    return model.encoder(feats) if lens is None else model.encoder(feats, input_lengths=lens)
 
 
 @torch.no_grad()
-def transformer_ctc_logits(model, spectrum):
-    """Front end and encoder as in `evaluate`, then the CTC head: (fp32 logits [B*T', Vp], B, T')."""
+def transformer_evaluate(model, spectrum, text, input_lengths=None):
+    """Transformer.evaluate (model.py:201-206); input_lengths as in transformer()."""
+    lens = pad_lengths(model, input_lengths)
+    enc = _encode(model, spectrum, lens)
+    return model.decoder.evaluate(text, enc) if lens is None else model.decoder.evaluate(text, enc, enc_lengths=lens)
+
+
+@torch.no_grad()
+def transformer_ctc_logits(model, spectrum, input_lengths=None):
+    """Front end and encoder as in `evaluate`, then the CTC head: (fp32 logits [B*T', Vp], B, T').  input_lengths: as in
+    transformer() (mask_padding models: the encoder masks the padded frames)."""
     if getattr(model, "ctc_head", None) is None:
         raise RuntimeError("asrx: the model has no CTC head (build it with Transformer(..., ctc=True))")
-    return _ctc_logits_of(model, model.encoder(model.input_layer(spectrum)))
+    return _ctc_logits_of(model, _encode(model, spectrum, pad_lengths(model, input_lengths)))
 
 
 @torch.no_grad()
@@ -880,7 +935,7 @@ def _ctc_logits_of(model, enc):
 
 @torch.no_grad()
 def transformer_ctc_greedy(model, spectrum, input_lengths=None):
-    logits, B, T = transformer_ctc_logits(model, spectrum)
+    logits, B, T = transformer_ctc_logits(model, spectrum, input_lengths)
     if input_lengths is not None:
         input_lengths = input_lengths.to(device=logits.device, dtype=torch.int32).contiguous()
     return K.ctc_greedy(logits, model.ctc_head.V, T, model.ctc_blank, input_lengths)
@@ -890,7 +945,7 @@ def transformer_ctc_greedy(model, spectrum, input_lengths=None):
 def transformer_align(model, spectrum, text, mask=None, input_lengths=None, *, bos_token_id=1):
     """Transformer.align: front end, encoder and CTC head, the transcript's CTC targets as the Trainer builds them
     (asrx_ctc_targets: `text` (B, n) where mask >= 1, without BOS / EOS / PAD), then asrx_ctc_align."""
-    logits, B, T = transformer_ctc_logits(model, spectrum)
+    logits, B, T = transformer_ctc_logits(model, spectrum, input_lengths)
     dev = logits.device
     dec = model.decoder
     drop = [int(bos_token_id), int(dec._eos_token_id)]
@@ -997,7 +1052,7 @@ def decoder_ctc_beam_search(dec, ctc, B, beam=8, nbest=1, max_len=None):
 
 @torch.no_grad()
 def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None,
-                    lm=None, lm_weight=0.0, token_bonus=0.0):
+                    lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
     """Two-pass decoding ("attention rescoring"): asrx_ctc_prefix_beam yields `beam` complete hypotheses per sample
     from the CTC head's logits alone; ONE teacher-forced decoder forward over all B * beam of them (rows BOS, labels;
     targets labels, EOS; cross-attention grouped per sample, nothing expanded) gives each log p_att, and they are
@@ -1015,7 +1070,10 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     lm (an asrx.NgramLM on the device) with lm_weight = beta > 0: the rank is log p_att + ctc_weight * log p_ctc +
     beta * log p_lm + token_bonus * len, the LM over the labels and the EOS after its sentence start.  One more launch
     (asrx_ngram_seq_logprob, which folds the CTC term in; asrx_rescore_rank then adds the two sums), and `lm_scores`
-    is filled.  lm=None or lm_weight = 0 (default) issues exactly the launches above."""
+    is filled.  lm=None or lm_weight = 0 (default) issues exactly the launches above.
+
+    enc_lengths (valid rows of each encoder output): the second pass's cross-attention masks the padded rows, one row
+    of key validity per sample for its `beam` hypotheses.  None (default): the launches above."""
     lam = float(ctc_weight)
     if lam != lam or lam < 0.0:
         raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
@@ -1045,7 +1103,8 @@ def decoder_rescore(dec, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm
     dec_in, dec_tgt, mask = K.hyp_tokens(tok, lens, n_hyp, B, W, L, BOS_ID, eos, pad, IGNORE_ID)
     enc_c = torch.empty(B * Te, d, dtype=C.cd, device=dev)
     K.cast(enc_x.reshape(B * Te, d).contiguous(), enc_c)
-    logits, _ = decoder_fwd(C, dec, dec_in, mask, enc_c, R, L, Te, final_norm=final_norm, group=W)
+    logits, _ = decoder_fwd(C, dec, dec_in, mask, enc_c, R, L, Te, final_norm=final_norm, group=W,
+                            xspec=key_spec(enc_lengths, B, Te, dev)[1])
     att = K.seq_logprob(logits, cls.V, dec_tgt, IGNORE_ID, n_hyp, W)
     if beta > 0.0:
         lm_s, rest = K.ngram_seq_logprob(lm, dec_tgt, IGNORE_ID, n_hyp, W, cscore, lam, beta, bonus)
@@ -1082,7 +1141,7 @@ def transformer_ctc_beam_search(model, spectrum, beam=8, input_lengths=None, nbe
     if getattr(model, "ctc_head", None) is None:
         raise RuntimeError("asrx: CTC beam search needs a model with a CTC head (Transformer(..., ctc=True))")
     _check_beam(beam, nbest)
-    logits, B, T = transformer_ctc_logits(model, spectrum)
+    logits, B, T = transformer_ctc_logits(model, spectrum, input_lengths)
     ctc = (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V)
     return decoder_ctc_beam_search(model.decoder, ctc, B, beam, nbest, max_len)
 
@@ -1098,11 +1157,12 @@ def transformer_rescore(model, spectrum, beam=8, ctc_weight=0.5, input_lengths=N
         raise ValueError(f"ctc_weight {ctc_weight} must be >= 0")
     _check_beam(beam, nbest)
     check_lm(lm, lm_weight, token_bonus, model.decoder._classifier.V)
+    lens = pad_lengths(model, input_lengths)
     with torch.no_grad():
-        enc = model.encoder(model.input_layer(spectrum))
+        enc = _encode(model, spectrum, lens)
     logits, B, T = _ctc_logits_of(model, enc)
     return decoder_rescore(model.decoder, enc, (logits, T, model.ctc_blank, input_lengths, model.ctc_head.V), beam,
-                           lam, nbest, final_norm, max_len, mbr_scale, lm, lm_weight, token_bonus)
+                           lam, nbest, final_norm, max_len, mbr_scale, lm, lm_weight, token_bonus, enc_lengths=lens)
 
 
 # ------------------------------------------------------------------------------------------- sub-modules

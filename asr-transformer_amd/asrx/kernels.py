@@ -567,6 +567,13 @@ class MaskSpec:
         return MaskSpec(1, True, valid, valid, valid.stride(0))
 
     @staticmethod
+    def keys(valid):
+        """Padded batches: key j of batch b takes part where valid[b, j] != 0 (uint8 [B, >= Lk], as
+        length_mask writes it); every query row attends, nothing is causal."""
+        assert valid.dtype == torch.uint8 and valid.dim() == 2 and valid.stride(1) == 1
+        return MaskSpec(1, False, valid, None, valid.stride(0))
+
+    @staticmethod
     def from_attention_mask(m, B, Lq, Lk):
         """Any-dtype mask broadcastable to (B, Lq, Lk); nonzero (>0) means masked (layers.py:22-23)."""
         if m is None:
@@ -937,6 +944,25 @@ def step_tokens(text, inp, mask):
     call("asrx_step_tokens", text.data_ptr(), text.stride(0), inp.data_ptr(), inp.stride(0), mask.data_ptr(),
          mask.stride(0), B, L, dec_in.data_ptr(), tgt.data_ptr(), valid.data_ptr(), stream())
     return dec_in, tgt, valid
+
+
+def length_mask(lengths, T, subsample=0, enc_len=None, valid=None):
+    """(enc_len int32 [B], valid uint8 [B, T]) of int32 device lengths [B] in one launch (asrx_length_mask, DESIGN.md
+    §18): enc_len = clamp(the k3/s2 length arithmetic applied `subsample` times, 0, T), valid[b, t] = t < enc_len[b].
+    enc_len / valid: buffers to write into (a captured step's) instead of fresh ones."""
+    _cuda(lengths, enc_len, valid)
+    if lengths.dtype != torch.int32 or lengths.dim() != 1 or not lengths.is_contiguous():
+        raise ValueError(f"asrx: lengths must be a contiguous int32 vector, got {lengths.dtype} {tuple(lengths.shape)}")
+    B, T = lengths.numel(), int(T)
+    if enc_len is None:
+        enc_len = torch.empty(B, dtype=torch.int32, device=lengths.device)
+    if valid is None:
+        valid = torch.empty(B, T, dtype=torch.uint8, device=lengths.device)
+    assert enc_len.dtype == torch.int32 and enc_len.is_contiguous() and enc_len.numel() == B
+    assert valid.dtype == torch.uint8 and valid.shape == (B, T) and valid.stride(1) == 1 and valid.stride(0) >= T
+    call("asrx_length_mask", lengths.data_ptr(), B, T, int(subsample), enc_len.data_ptr(), valid.data_ptr(),
+         valid.stride(0), stream())
+    return enc_len, valid
 
 
 def _planes(t, name):

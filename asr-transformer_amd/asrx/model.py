@@ -5,7 +5,9 @@ evaluate signatures, same state_dict keys.  Whole stacks run as explicit native 
 
 Extra keyword-only knobs (not in the reference): precision ("bf16" training path | "fp32" parity path),
 attention ("fused" LDS-tiled kernel | "unfused" materialised scores + row softmax), ctc / ctc_blank (Transformer
-only: a CTC head on the encoder output, one extra state_dict key `ctc_head.weight`).
+only: a CTC head on the encoder output, one extra state_dict key `ctc_head.weight`), mask_padding (Transformer only:
+the entry points that take `input_lengths` also mask the padded frames in the encoder's self-attention and in the
+cross-attention; a plain attribute, no state_dict key).
 """
 import math
 import weakref
@@ -148,9 +150,12 @@ class Encoder(nn.Module):
         self._layers = nn.ModuleList([EncoderLayer(emb_dim, num_heads, ff_dim, dropout) for _ in range(num_layers)])
         _adopt(self)
 
-    def forward(self, x):
+    def forward(self, x, input_lengths=None):
+        """input_lengths (B,): the valid rows (encoder frames) of each utterance; every layer's self-attention then
+        masks the keys behind them.  The padding must be finite; the valid rows of the output are a
+        function of the valid frames only, the padded rows are finite but unspecified.  None: no mask (model.py:21)."""
         from .functions import encoder
-        return encoder(self, x)
+        return encoder(self, x, input_lengths)
 
 
 class DecoderLayer(nn.Module):
@@ -190,40 +195,53 @@ class Decoder(nn.Module):
         self._classifier = _Classifier(emb_dim, vocab_size)
         _adopt(self)
 
-    def forward(self, x, mask, enc_x):
+    def forward(self, x, mask, enc_x, enc_lengths=None):
+        """enc_lengths (B,): the valid rows of each encoder output; every layer's cross-attention then masks the rows
+        behind them (an utterance with no valid row gets a zero cross-attention).  None: no mask
+        (model.py:71)."""
         from .functions import decoder
-        return decoder(self, x, mask, enc_x)
+        return decoder(self, x, mask, enc_x, enc_lengths)
 
-    def evaluate(self, x, enc_x):
+    def evaluate(self, x, enc_x, enc_lengths=None):
+        """enc_lengths: as in forward."""
         from .functions import decoder_evaluate
-        return decoder_evaluate(self, x, enc_x)
+        return decoder_evaluate(self, x, enc_x, enc_lengths)
 
     def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
-                    ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0):
+                    ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
         """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult.
-        lm / lm_weight / token_bonus: shallow fusion with an asrx.NgramLM on the device."""
+        lm / lm_weight / token_bonus: shallow fusion with an asrx.NgramLM on the device.  enc_lengths: as in forward."""
         from .functions import decoder_beam_search
         return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
-                                   ctc_weight, lm, lm_weight, token_bonus)
+                                   ctc_weight, lm, lm_weight, token_bonus, enc_lengths)
 
     def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None,
-                lm=None, lm_weight=0.0, token_bonus=0.0):
+                lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
         """Two-pass decoding from an encoder output and its CTC logits, ctc = (logits, T, blank, input_lengths) as in
         beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult.  mbr_scale: a number
         orders the hypotheses by minimum Bayes risk under softmax(mbr_scale * score) and fills `risks`.  lm (an
         asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank and
-        fills `lm_scores`."""
+        fills `lm_scores`.  enc_lengths: as in forward, for the second pass's cross-attention."""
         from .functions import decoder_rescore
         return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len, mbr_scale, lm,
-                               lm_weight, token_bonus)
+                               lm_weight, token_bonus, enc_lengths)
 
 
 class Transformer(nn.Module):
-    """model.py:154-206.  forward(spectrum (B,1,F,T), text (B,L) int, mask (B,L)) -> logits (B,L,V)."""
+    """model.py:154-206.  forward(spectrum (B,1,F,T), text (B,L) int, mask (B,L)) -> logits (B,L,V).
+
+    mask_padding=True (keyword-only, default False; a plain attribute that may be set after loading): every entry
+    point that takes `input_lengths` — valid ENCODER frames per utterance, asrx.subsampled(spectrogram frames) —
+    also masks the keys behind them in the encoder's self-attention and in the decoder's cross-attention (DESIGN.md
+    §18).  The contract: the padding must be finite (a masked NaN value row still poisons 0 * NaN); the valid rows of
+    every output are then a function of the valid frames only, whatever the utterance is batched with; padded encoder
+    rows are finite but unspecified; an utterance shorter than 7 spectrogram frames (0 encoder frames) gives finite
+    outputs with a zero cross-attention, and no gradient.  With the flag off, or without input_lengths, every call
+    runs launch for launch as it did before the flag existed (no key mask: model.py:21,71)."""
 
     def __init__(self, vocab_size, input_dim, embedding_dim, decoder_seq_len, encoder_seq_len, encoder_num_layers,
                  decoder_num_layers, num_heads, ff_dim, dropout=0.1, pad_token_id=4, eos_token_id=2, *,
-                 precision="bf16", attention="fused", ctc=False, ctc_blank=None):
+                 precision="bf16", attention="fused", ctc=False, ctc_blank=None, mask_padding=False):
         super().__init__()
         self.input_layer = FrontEnd()
         n_freq = subsampled(input_dim)
@@ -237,6 +255,7 @@ class Transformer(nn.Module):
                                eos_token_id=eos_token_id, dropout=dropout, pad_token_id=pad_token_id)
         self.precision = precision
         self.attention = attention
+        self.mask_padding = bool(mask_padding)
         # ctc=True: a bias-free linear head on the encoder output (after Encoder._norm_out) for the hybrid
         # CTC/attention objective (asrx.train.Trainer(ctc_weight=...)) and decoder-free best-path decoding.  Registered
         # last, so every other parameter keeps its key, its initial values under a given seed and its place in the
@@ -248,27 +267,31 @@ class Transformer(nn.Module):
             self.ctc_head = _Classifier(embedding_dim, vocab_size)
         _adopt(self)
 
-    def forward(self, spectrum, text, mask):
+    def forward(self, spectrum, text, mask, input_lengths=None):
+        """input_lengths (B,): valid encoder frames per utterance; used where mask_padding is set (see the class)."""
         from .functions import transformer
-        return transformer(self, spectrum, text, mask)
+        return transformer(self, spectrum, text, mask, input_lengths)
 
-    def evaluate(self, spectrum, text):
+    def evaluate(self, spectrum, text, input_lengths=None):
+        """input_lengths: as in forward."""
         from .functions import transformer_evaluate
-        return transformer_evaluate(self, spectrum, text)
+        return transformer_evaluate(self, spectrum, text, input_lengths)
 
     def beam_search(self, spectrum, text=None, ctc_weight=0.0, input_lengths=None, **kw):
         """Front end, encoder, then Decoder.beam_search(text, enc, **kw); text=None is a BOS column (id 1).
         ctc_weight in (0, 1] (ctc=True models): joint CTC/attention decoding, hypotheses ranked by
-        (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc; input_lengths: valid encoder frames per sample.
+        (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc; input_lengths: valid encoder frames per sample (with
+        mask_padding they also mask the padded frames in the encoder and the cross-attention, at any ctc_weight).
         lm=, lm_weight=, token_bonus= (an asrx.NgramLM on the device): shallow fusion, every generated token also
         earns lm_weight * log p_lm + token_bonus; lm=None or lm_weight=0 is the search without an LM."""
         from .functions import transformer_beam_search
         return transformer_beam_search(self, spectrum, text, ctc_weight, input_lengths, **kw)
 
-    def ctc_logits(self, spectrum):
-        """Front end, encoder and the CTC head (ctc=True models), no grad: fp32 logits (B, T', V)."""
+    def ctc_logits(self, spectrum, input_lengths=None):
+        """Front end, encoder and the CTC head (ctc=True models), no grad: fp32 logits (B, T', V).  input_lengths: as
+        in forward (the rows behind them are then unspecified)."""
         from .functions import transformer_ctc_logits
-        logits, B, T = transformer_ctc_logits(self, spectrum)
+        logits, B, T = transformer_ctc_logits(self, spectrum, input_lengths)
         return logits.view(B, T, -1)[:, :, :self.ctc_head.V]
 
     def ctc_greedy(self, spectrum, input_lengths=None):
@@ -304,7 +327,9 @@ class Transformer(nn.Module):
         """Two-pass decoding (ctc=True models): ctc_beam_search's `beam` hypotheses, one teacher-forced decoder forward
         over all of them, ranked by log p_att + ctc_weight * log p_ctc.  Returns a RescoreResult: a BeamResult
         filled as beam_search fills it (tokens BOS, labels, EOS...; lengths count the EOS; scores combined) with
-        att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample (the CTC frames only).
+        att_scores and ctc_scores besides.  input_lengths: valid encoder frames per sample: the first pass's CTC
+        frames, and with mask_padding also the keys of the encoder's self-attention and of the second pass's
+        cross-attention.
         mbr_scale = a number >= 0: the order is the minimum-Bayes-risk one under softmax(mbr_scale * score) over the
         `beam` hypotheses (asrx_edit_distance + asrx_mbr_rank on the device) and `risks` is filled; None: as before.
         lm (an asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank

@@ -17,6 +17,11 @@ the CTC launches (head GEMM, asrx_ctc_targets, asrx_ctc_loss, head data gradient
 
 `Trainer(..., spec_augment=asrx.SpecAugment(...))` trains step n on step n's SpecAugment of its spectrogram: one
 asrx_specaug launch that takes the place of the spectrogram's copy into the captured input buffer.
+
+On a `Transformer(..., mask_padding=True)`, `step(..., input_lengths=)` (spectrogram frames) trains a padded batch as if
+every utterance stood alone: one asrx_length_mask launch inside the step turns the lengths into the encoder's row counts
+and key-validity bytes, which mask the encoder's self-attention and the cross-attention and bound the CTC term
+(DESIGN.md §18).  In graph mode the lengths are one more static input, the launch part of the captured step.
 """
 import os
 
@@ -26,7 +31,7 @@ from . import kernels as K
 from .augment import rank_seed
 from .blocks import FreshGrads
 from .dist import GradAllReduce
-from .functions import get_store, make_ctx, model_backward, model_forward
+from .functions import get_store, key_spec, make_ctx, model_backward, model_forward, pad_lengths
 
 # weight gradients whose only writer is one weight-gradient GEMM are not zeroed before the backward: that GEMM
 # writes them with beta = 0 (blocks.FreshGrads).  ASRX_FRESH_GRADS=0 zeroes the whole buffer instead (A/B).
@@ -313,9 +318,10 @@ class Trainer:
         self.spec_augment = spec_augment
         self._aug_buf = None
         # ctc_weight w > 0: the hybrid objective (1 - w) * CE + w * CTC_mean, the CTC term on the model's ctc_head
-        # (Transformer(..., ctc=True)) over all T' encoder frames, its targets the step's text without BOS / EOS / PAD
-        # (asrx_ctc_targets), zero_infinity on.  w = 0 is the cross-entropy step, launch for launch; a ctc_head the
-        # model may carry is then frozen like the reference's unused parameters (no gradient, no AdamW, no decay).
+        # (Transformer(..., ctc=True)) over all T' encoder frames (over each utterance's own frames where the step masks
+        # padding, see step), its targets the step's text without BOS / EOS / PAD (asrx_ctc_targets), zero_infinity on.
+        # w = 0 is the cross-entropy step, launch for launch; a ctc_head the model may carry is then frozen like the
+        # reference's unused parameters (no gradient, no AdamW, no decay).
         self.ctc_weight = float(ctc_weight)
         if not 0.0 <= self.ctc_weight < 1.0:
             raise ValueError(f"ctc_weight {ctc_weight} outside [0, 1)")
@@ -385,24 +391,30 @@ class Trainer:
             self._rspans[key] = tab
         return tab
 
-    def forward_backward(self, spectrum, text, mask, ready=None, capture=False, input_text=None):
+    def forward_backward(self, spectrum, text, mask, ready=None, capture=False, input_text=None, input_lengths=None):
         """text: (B, L+1) with BOS ... ; inputs text[:, :-1], targets text[:, 1:] (train.py:24,32).  input_text
         (optional, (B, L+1)): the decoder input instead of text (train.py:22-25 feeds a shifted copy while the
         targets stay text[:, 1:]).  ready: gradient-range hook (default: the reducer's, when multi-GPU); capture:
-        building a HIP graph."""
+        building a HIP graph.  input_lengths (optional, [B], spectrogram frames; used on a mask_padding model): the
+        padded frames are masked in the encoder's self-attention and the cross-attention, and the CTC term runs over
+        each utterance's own encoder frames; read on the device, inside the step."""
         model = self.model
         C = make_ctx(model, model.decoder.p)
         inp = text if input_text is None else input_text
         lam = self.ctc_weight
+        from .model import subsampled
+        enc_len, enc_spec = key_spec(pad_lengths(model, input_lengths), spectrum.shape[0],
+                                     subsampled(spectrum.shape[-1]), self.store.flat.device, 2)
         if (text.is_cuda and text.dtype == torch.int64 and inp.dtype == torch.int64 and mask.dtype == torch.float32
                 and text.stride(1) == 1 and inp.stride(1) == 1 and mask.stride(1) == 1):
             # the shifted inputs, targets and decoder mask in one native launch (no torch copies in the step)
             B, L = text.shape[0], text.shape[1] - 1
             dec_in, tgt, valid = K.step_tokens(text, inp, mask)
             spec = K.MaskSpec(1, True, valid, valid, valid.stride(0))
-            logits, S = model_forward(C, model, spectrum, dec_in.view(B, L), None, spec=spec, ctc=lam > 0)
+            logits, S = model_forward(C, model, spectrum, dec_in.view(B, L), None, spec=spec, ctc=lam > 0,
+                                      enc_spec=enc_spec)
         else:
-            logits, S = model_forward(C, model, spectrum, inp[:, :-1], mask[:, :-1], ctc=lam > 0)
+            logits, S = model_forward(C, model, spectrum, inp[:, :-1], mask[:, :-1], ctc=lam > 0, enc_spec=enc_spec)
             tgt = text[:, 1:].reshape(-1).contiguous()
         V = model.decoder._classifier.V
         loss, dl, am = K.cross_entropy(logits, V, tgt, ignore_index=self.ignore_index, grad_scale=1.0 - lam,
@@ -419,7 +431,7 @@ class Trainer:
             cl = S["ctc_logits"]
             Tp = cl.shape[0] // text.shape[0]
             # (a row longer than the kernel's 255 labels has no alignment there: zero_infinity drops it)
-            loss, _, dctc = K.ctc_loss(cl, model.ctc_head.V, Tp, ctc_tgt, ctc_len,
+            loss, _, dctc = K.ctc_loss(cl, model.ctc_head.V, Tp, ctc_tgt, ctc_len, input_lengths=enc_len,
                                        max_target_len=min(ctc_tgt.shape[1], 255), blank=model.ctc_blank,
                                        reduction="mean", zero_infinity=True, grad_scale=lam, grad_dtype=C.cd,
                                        loss_add=loss, loss_add_scale=1.0 - lam, loss_scale=lam)
@@ -503,18 +515,22 @@ class Trainer:
         """One training step (forward, CE, backward, all-reduce, AdamW).  Returns the loss as a device scalar; in
         graph mode it is the captured output tensor, overwritten by the next step.  input_text: see
         forward_backward.  input_lengths (optional, [B]): the valid frames of each spectrogram, for the augmenter
-        (Trainer(..., spec_augment=...)); the caller's spectrogram is never written."""
+        (Trainer(..., spec_augment=...)); the caller's spectrogram is never written.  On a model with mask_padding
+        they also mask the padded frames in the encoder's self-attention and the cross-attention and bound the CTC term
+        (forward_backward; the padding must be finite); without the flag, or without lengths, the step runs launch for
+        launch as before."""
         if input_text is None:
             input_text = text
+        lens = pad_lengths(self.model, input_lengths, self.store.flat.device)
         if self.graph and self.model.precision == "bf16":
-            key = self._key(spectrum, text, mask, input_text)
+            key = self._key(spectrum, text, mask, input_text) + (("lengths",) if lens is not None else ())
             self._cap = self._caps.get(key)
             # a new input shape runs one eager step first (kernel objects, allocator), then is captured and kept
             if self._cap is None and self.step_count >= GRAPH_WARMUP and key in self._eager_keys:
-                self._capture(spectrum, text, mask, input_text)
+                self._capture(spectrum, text, mask, input_text, lens)
                 self._caps[key] = self._cap
             if self._cap is not None:
-                return self._replay(spectrum, text, mask, input_text, input_lengths)
+                return self._replay(spectrum, text, mask, input_text, input_lengths, lens)
             self._eager_keys.add(key)
         if self.spec_augment is not None:
             spectrum = self._augment(spectrum, None, input_lengths, self.step_count + 1)
@@ -523,7 +539,7 @@ class Trainer:
         # AdamW of the trainer takes 1/sqrt(bias_corr2) from the same device arithmetic
         K.adam_hyper(self._hyp, self.lr, self.betas[0], self.betas[1], self.step_count + 1)
         try:
-            loss = self.forward_backward(spectrum, text, mask, input_text=input_text)
+            loss = self.forward_backward(spectrum, text, mask, input_text=input_text, input_lengths=lens)
         finally:
             self._fuse_next = False
         self.step_count += 1
@@ -549,9 +565,11 @@ class Trainer:
     def _key(*xs):
         return tuple((tuple(x.shape), x.dtype) for x in xs)
 
-    def _capture(self, spectrum, text, mask, input_text):
+    def _capture(self, spectrum, text, mask, input_text, lens=None):
         dev = self.store.flat.device
         ins = tuple(x.to(dev).clone() for x in (spectrum, text, mask, input_text))
+        if lens is not None:   # one more static input: the captured asrx_length_mask launch reads it at every replay
+            ins += (lens.clone(),)
         torch.cuda.synchronize(dev)
         pool = torch.cuda.graph_pool_handle()
         side = torch.cuda.Stream(device=dev)
@@ -562,7 +580,7 @@ class Trainer:
             self._fuse_next = self._fused_adam_ok()
             try:
                 loss = self.forward_backward(*ins[:3], ready=seg if self.reducer.active else None, capture=True,
-                                             input_text=ins[3])
+                                             input_text=ins[3], input_lengths=ins[4] if lens is not None else None)
                 if not self.reducer.active:
                     self._adam(self._hyp)
             finally:
@@ -573,14 +591,15 @@ class Trainer:
         torch.cuda.synchronize(dev)
         self._cap = (seg, ins, loss, self.last_preds)
 
-    def _replay(self, spectrum, text, mask, input_text, input_lengths=None):
+    def _replay(self, spectrum, text, mask, input_text, input_lengths=None, lens=None):
         seg, ins, loss, preds = self._cap
         aug = self.spec_augment is not None
         if aug and ins[0].data_ptr() == spectrum.data_ptr():
             raise ValueError("Trainer.step: the spectrogram is the captured input buffer itself; the augmenter does not "
                              "work in place, pass a tensor of your own")
         self.last_preds = preds
-        for i, (dst, src) in enumerate(zip(ins, (spectrum, text, mask, input_text))):
+        srcs = (spectrum, text, mask, input_text) + ((lens,) if lens is not None else ())
+        for i, (dst, src) in enumerate(zip(ins, srcs)):
             if i == 0 and aug:   # the augmenting launch is this buffer's copy
                 self._augment(src, dst, input_lengths, self.step_count + 1)
             elif dst.data_ptr() != src.data_ptr():

@@ -40,7 +40,8 @@ extern "C" {
  * minimum-Bayes-risk selection: asrx_edit_distance, asrx_mbr_rank.  10: n-gram LM shallow fusion: asrx_ngram_score,
  * asrx_ngram_advance, asrx_ngram_seq_logprob.  11: SpecAugment while the spectrogram is copied: asrx_specaug.
  * 12: log-mel filterbank features and CMVN: asrx_logmel, asrx_logmel_pass, asrx_stft_power, asrx_cmvn,
- * asrx_feature_stats). */
+ * asrx_feature_stats.  13: padded batches: asrx_length_mask turns lengths into the key-validity bytes of mask mode
+ * 1). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -812,6 +813,23 @@ int asrx_cmvn(const float* x, float* out, int32_t B, int32_t F, int32_t T, int64
               float pad_value, void* stream);
 int asrx_feature_stats(const float* x, int32_t B, int32_t F, int32_t T, int64_t x_bstride, const int32_t* lengths,
                        double* sum, double* sumsq, int64_t* count, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Padded batches (version >= 13): lengths -> the encoder's row counts and the per-batch key-validity
+ * bytes that mask mode 1 of asrx_attention_fwd / asrx_attention_bwd / asrx_softmax_fwd takes as kvalid (qvalid NULL,
+ * not causal: every query row attends to the valid keys only).  One launch, no host synchronisation, safe under
+ * stream capture: a captured training step replays with new lengths.
+ *
+ * lengths int32 [B] (device) -> enc_lengths int32 [B] and valid uint8 [B][valid_bstride] (either may be NULL, not
+ * both).
+ * subsample = k >= 0: the unpadded kernel-3 stride-2 length arithmetic n -> (n - 3) / 2 + 1 (0 for n < 3) applied k
+ * times (the front end is k = 2, asrx.subsampled; k = 0: lengths are rows already).  The result is clamped to [0, T];
+ * valid[b*valid_bstride + t] = t < enc_lengths[b] for t < T; columns [T, valid_bstride) are not written.
+ * Negative lengths give 0.  Before any HIP call: null lengths, B < 0, T <= 0, subsample outside 0..8, both outputs
+ * null or valid_bstride < T return ASRX_ERR_ARG; B = 0 returns 0 with nothing launched.
+ * ------------------------------------------------------------------------------------------------- */
+int asrx_length_mask(const int32_t* lengths, int32_t B, int32_t T, int32_t subsample, int32_t* enc_lengths,
+                     uint8_t* valid, int64_t valid_bstride, void* stream);
 
 /* Data-parallel gradient exchange on a bf16 wire (asrx.dist.GradAllReduce, wire="bf16"; the reference trains on one
  * device, train.py:16-35, so this is the build's own DDP step): in = the W peers' bf16 copies of one chunk of c
