@@ -10,6 +10,7 @@ from .kernels import CtcAlignment  # noqa: F401
 from .augment import SpecAugment  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401
 from .features import CMVN, LogMel  # noqa: F401
+from .loss import CrossEntropyLoss  # noqa: F401
 from .lm import NgramLM  # noqa: F401
 from .model import Decoder, DecoderLayer, Encoder, EncoderLayer, FrontEnd, Transformer, subsampled  # noqa: F401
 from .score import EditCounts, ErrorRate, MbrResult, edit_distance, mbr_rerank  # noqa: F401

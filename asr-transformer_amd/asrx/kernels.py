@@ -1195,20 +1195,56 @@ def embed_bwd(tok, dout, dtable, L, pad_id, dropout_p=0.0, seed=0):
          pad_id, dropout_p, seed & _U64, dtable.data_ptr(), stream())
 
 
-def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_grad=True, want_argmax=False):
+CE_OLD_MAXLD = 1024   # frontend.hip: the longest row asrx_cross_entropy (one wave per row) takes
+
+
+def xent_workspace_elems(rows):
+    """fp32 workspace elements of asrx_cross_entropy_ls (asrx_xent_workspace_elems: the C-ABI's own size rule)."""
+    from ._lib import lib
+    n = lib().asrx_xent_workspace_elems(rows)
+    if n < 0:
+        raise RuntimeError(f"asrx: no cross-entropy workspace for {rows} rows")
+    return n
+
+
+def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_grad=True, want_argmax=False,
+                  label_smoothing=0.0, grad_dtype=torch.bfloat16, want_stats=False, strided=False):
     """logits fp32 [rows, ld], rows contiguous (the kernel writes dlogits with the logits' row stride, so a
-    row-strided view is refused); returns (loss[1], dlogits bf16 [rows, ld] or None, argmax or None)."""
+    row-strided view is refused); returns (loss[1], dlogits [rows, ld] in grad_dtype or None, argmax or None), and
+    with want_stats a fourth value: stats fp32 [2] = (mean unsmoothed nll, token accuracy) over the rows that count.
+    label_smoothing 0, ld <= 1024, bf16 gradients and no stats is asrx_cross_entropy, as ever; everything else is
+    asrx_cross_entropy_ls (any V <= 2^20).  strided=True (that entry point only) takes a view
+    [rows, >= V] of wider rows on purpose: its row stride is the ld of the logits and of dlogits, and the columns past
+    V are never read."""
     _cuda(logits, target)
     rows, ld = logits.shape
-    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
-        "asrx: cross_entropy needs contiguous fp32 logits [rows, ld]"
+    if strided:
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and V <= ld, \
+            "asrx: cross_entropy(strided=True) needs fp32 rows of unit column stride"
+        if rows > 1:
+            ld = logits.stride(0)
+            assert ld >= logits.shape[1], "asrx: cross_entropy(strided=True): overlapping rows"
+    else:
+        assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.stride(0) == ld, \
+            "asrx: cross_entropy needs contiguous fp32 logits [rows, ld]"
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"asrx: label_smoothing {label_smoothing} outside [0, 1)")
     loss = torch.empty(1, device=logits.device, dtype=torch.float32)
-    dl = torch.empty(rows, ld, device=logits.device, dtype=torch.bfloat16) if want_grad else None
+    dl = torch.empty(rows, ld, device=logits.device, dtype=grad_dtype) if want_grad else None
     am = torch.empty(rows, device=logits.device, dtype=torch.int64) if want_argmax else None
-    ws = torch.empty(rows + 2, device=logits.device, dtype=torch.float32)
-    call("asrx_cross_entropy", logits.data_ptr(), rows, V, logits.stride(0), target.data_ptr(), ignore_index,
-         grad_scale, loss.data_ptr(), _p(dl), _p(am), ws.data_ptr(), stream())
-    return loss, dl, am
+    if label_smoothing == 0.0 and ld <= CE_OLD_MAXLD and grad_dtype == torch.bfloat16 and not (want_stats or strided):
+        ws = torch.empty(rows + 2, device=logits.device, dtype=torch.float32)
+        call("asrx_cross_entropy", logits.data_ptr(), rows, V, logits.stride(0), target.data_ptr(), ignore_index,
+             grad_scale, loss.data_ptr(), _p(dl), _p(am), ws.data_ptr(), stream())
+        return loss, dl, am
+    gcode = {torch.bfloat16: BF16, torch.float32: F32}.get(grad_dtype)
+    if gcode is None:
+        raise TypeError(f"asrx: cross_entropy gradients are bf16 or fp32, not {grad_dtype}")
+    stats = torch.empty(2, device=logits.device, dtype=torch.float32) if want_stats else None
+    ws = torch.empty(xent_workspace_elems(rows), device=logits.device, dtype=torch.float32)
+    call("asrx_cross_entropy_ls", logits.data_ptr(), rows, V, ld, target.data_ptr(), ignore_index,
+         label_smoothing, grad_scale, loss.data_ptr(), _p(stats), gcode, _p(dl), _p(am), ws.data_ptr(), stream())
+    return (loss, dl, am, stats) if want_stats else (loss, dl, am)
 
 
 CTC_REDUCTIONS = {"sum": CTC_SUM, "mean": CTC_MEAN}

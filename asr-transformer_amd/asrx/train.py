@@ -310,8 +310,17 @@ class Trainer:
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.98), eps=1e-9, weight_decay=0.0, decoupled=True,
                  ignore_index=-100, group=None, bucket_mb=64, allreduce_fn=None, graph=None, wire=None, preds=False,
-                 ctc_weight=0.0, bos_token_id=1, spec_augment=None):
+                 ctc_weight=0.0, bos_token_id=1, spec_augment=None, label_smoothing=0.0):
         self.model = model
+        # label_smoothing eps > 0: the cross-entropy term is nn.CrossEntropyLoss(label_smoothing=eps)'s, the uniform mass
+        # over the V classes (asrx_cross_entropy_ls); a launch constant, the same in an eager and a
+        # captured step.  That entry point also takes the vocabularies beyond 1024 at any eps, and leaves last_stats:
+        # device fp32 [2] = (mean unsmoothed nll, token accuracy) of the step (in graph mode the captured buffer,
+        # overwritten by the next step), None where the step ran asrx_cross_entropy (eps = 0, Vp <= 1024: as ever).
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing {label_smoothing} outside [0, 1)")
+        self.last_stats = None
         # spec_augment (asrx.SpecAugment): step n (1-based, the replay's seed offset) trains on the augmentation of
         # step n of its spectrogram, one asrx_specaug launch: into a buffer of the trainer's in an eager step, into the
         # captured input buffer, in place of the copy, before a replay.  None: the step launch for launch as without.
@@ -343,7 +352,7 @@ class Trainer:
         self.store.refresh_shadow(force=True)
         self._wonly = [p for p in wgrad_only_params(model) if not any(p is q for q in idle_head)] if FRESH_GRADS else []
         self.graph = GRAPH if graph is None else bool(graph)
-        self._cap = None        # captured step of the current input shape: (segments, static inputs, loss, preds)
+        self._cap = None        # captured step of the current input shape: (segments, static inputs, loss, preds, stats)
         self._caps = {}         # every captured step, keyed by input shapes (a smaller last batch keeps its own graph)
         self._eager_keys = set()   # input shapes that have run one eager step (captured only after one)
         self._hyp = torch.zeros(3, dtype=torch.float32, device=self.store.flat.device)
@@ -417,8 +426,15 @@ class Trainer:
             logits, S = model_forward(C, model, spectrum, inp[:, :-1], mask[:, :-1], ctc=lam > 0, enc_spec=enc_spec)
             tgt = text[:, 1:].reshape(-1).contiguous()
         V = model.decoder._classifier.V
-        loss, dl, am = K.cross_entropy(logits, V, tgt, ignore_index=self.ignore_index, grad_scale=1.0 - lam,
-                                       want_argmax=self.want_preds)
+        if self.label_smoothing > 0 or logits.shape[1] > K.CE_OLD_MAXLD:
+            # (gradients in the model's compute dtype: an fp32 model's backward takes them as they are)
+            loss, dl, am, self.last_stats = K.cross_entropy(
+                logits, V, tgt, ignore_index=self.ignore_index, grad_scale=1.0 - lam, want_argmax=self.want_preds,
+                label_smoothing=self.label_smoothing, grad_dtype=C.cd, want_stats=True)
+        else:
+            loss, dl, am = K.cross_entropy(logits, V, tgt, ignore_index=self.ignore_index, grad_scale=1.0 - lam,
+                                           want_argmax=self.want_preds)
+            self.last_stats = None
         self.last_preds = am
         dctc = None
         if lam > 0:
@@ -589,15 +605,15 @@ class Trainer:
                 seg.close()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        self._cap = (seg, ins, loss, self.last_preds)
+        self._cap = (seg, ins, loss, self.last_preds, self.last_stats)
 
     def _replay(self, spectrum, text, mask, input_text, input_lengths=None, lens=None):
-        seg, ins, loss, preds = self._cap
+        seg, ins, loss, preds, stats = self._cap
         aug = self.spec_augment is not None
         if aug and ins[0].data_ptr() == spectrum.data_ptr():
             raise ValueError("Trainer.step: the spectrogram is the captured input buffer itself; the augmenter does not "
                              "work in place, pass a tensor of your own")
-        self.last_preds = preds
+        self.last_preds, self.last_stats = preds, stats
         srcs = (spectrum, text, mask, input_text) + ((lens,) if lens is not None else ())
         for i, (dst, src) in enumerate(zip(ins, srcs)):
             if i == 0 and aug:   # the augmenting launch is this buffer's copy

@@ -41,7 +41,8 @@ extern "C" {
  * asrx_ngram_advance, asrx_ngram_seq_logprob.  11: SpecAugment while the spectrogram is copied: asrx_specaug.
  * 12: log-mel filterbank features and CMVN: asrx_logmel, asrx_logmel_pass, asrx_stft_power, asrx_cmvn,
  * asrx_feature_stats.  13: padded batches: asrx_length_mask turns lengths into the key-validity bytes of mask mode
- * 1). */
+ * 1).  14: label-smoothed cross-entropy over vocabularies up to 2^20, with fp32 or bf16 gradients and perplexity /
+ * accuracy statistics: asrx_cross_entropy_ls, asrx_xent_workspace_elems). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -364,6 +365,29 @@ int asrx_embed_bwd(const int64_t* tok, int64_t ntok, int32_t L, const float* dou
 int asrx_cross_entropy(const float* logits, int64_t rows, int32_t V, int64_t ld, const int64_t* target,
                        int64_t ignore_index, float grad_scale, float* loss, void* dlogits, int64_t* argmax,
                        float* ws, void* stream);
+
+/* Label-smoothed cross-entropy over any V <= 2^20 (nn.CrossEntropyLoss(ignore_index=, label_smoothing=eps), mean
+ * reduction).  n = #rows with target != ignore_index; per valid row, lse = logsumexp over c < V:
+ *   nll = lse - x[t],  smooth = lse - mean_{c<V} x[c],  row = (1 - eps) * nll + eps * smooth
+ *   loss = sum row / n                                   (0 when n == 0)
+ *   dlogits[r][c] = grad_scale / n * (softmax_c - (1 - eps) * [c == t] - eps / V)   for c < V; 0 for V <= c < ld and
+ *                   in every column of an ignored row (nullable; grad_dtype ASRX_BF16 or ASRX_F32, row stride ld)
+ *   argmax[r]  first index of the row maximum over c < V, ignored rows included (nullable)
+ *   stats[0]   mean unsmoothed nll over the valid rows (log perplexity), stats[1] = #(valid, argmax == t) / n
+ *              (nullable [2]; both 0 when n == 0)
+ * The uniform mass is over the V classes, never over ld; columns [V, ld) of logits are never read.  eps > 0 assumes
+ * finite logits; at eps == 0, -inf in a non-target class is a class of probability 0.  Row sums are finished in a
+ * fixed order (no float atomics): the loss is bit-reproducible.  Rows of ld <= 16384 are read once; longer rows
+ * twice.  16-B loads where ld % 4 == 0 and logits / dlogits are 16-B aligned, 4-B ones otherwise.
+ * ws: asrx_xent_workspace_elems(rows) floats (3 rows + 4; -1 for rows < 0 and for rows beyond ASRX_XENT_MAX_ROWS, the
+ * most whose count an int holds, which asrx_cross_entropy_ls refuses as well).
+ * ASRX_ERR_ARG: null logits / target / loss / ws, V <= 0, ld < V, rows < 0, eps outside [0, 1), an unknown
+ * grad_dtype; ASRX_ERR_UNSUPPORTED: V > 2^20 or rows > ASRX_XENT_MAX_ROWS (all before any launch).  rows == 0 writes loss 0. */
+#define ASRX_XENT_MAX_ROWS 715827881
+int asrx_xent_workspace_elems(int64_t rows);
+int asrx_cross_entropy_ls(const float* logits, int64_t rows, int32_t V, int64_t ld, const int64_t* target,
+                          int64_t ignore_index, float label_smoothing, float grad_scale, float* loss, float* stats,
+                          int32_t grad_dtype, void* dlogits, int64_t* argmax, float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Elementwise utilities.
