@@ -242,33 +242,13 @@ def attn_prepare(C):
     return {"seed": C.seed(), "dropmask": None, "ready": False}
 
 
-# Where asrx_attention_fwd streams K/V through LDS (csrc/attention.hip: R_MAXK and take_stream of the dispatcher; a
-# superset of it, as stream_ok's further conditions only send fewer shapes there).  tests/test_lengths_cpu.py reads the
-# dispatcher's source and fails when these no longer state its thresholds.
-STREAM_ABOVE_LK = 256        # Lk > R_MAXK
-STREAM_FROM_LK = 128         # or STREAM_FROM_LK < Lk <= R_MAXK ...
-STREAM_FROM_LQ = 64          # ... with Lq > STREAM_FROM_LQ
-
-
-def _keys_need_unfused(spec, Lq, Lk, dh):
-    """A padded batch's key spec (MaskSpec.keys) where the fused forward would stream K/V (dh 64; Lk > 256, or
-    128 < Lk <= 256 with more than 64 queries) and Lk or the row stride of the validity bytes is no multiple of 4: the
-    streamed kernel moves the validity bytes as 4-byte words inside a range of Lk bytes from each row's base, so the
-    word that holds byte Lk - 1 is clipped whole and the last Lk % 4 keys read as invalid — for a full-length utterance
-    they are not — and a row base off a word boundary is not a word-wise read's to take.  Those
-    attentions take the materialised-scores program, whose row softmax reads the bytes one by one."""
-    keys_only = spec.mode == 1 and spec.kvalid is not None and spec.qvalid is None and not spec.causal
-    streams = Lk > STREAM_ABOVE_LK or (Lk > STREAM_FROM_LK and Lq > STREAM_FROM_LQ)
-    return keys_only and dh == 64 and streams and (Lk % 4 != 0 or spec.valid_bstride % 4 != 0)
-
-
 def attn_fwd(C, q, k, v, o, B, H, Lq, Lk, dh, strides, scale, spec, prep=None):
     """Fused LDS-tiled kernel on the bf16 path; materialised scores + row softmax otherwise."""
     if prep is None:
         prep = attn_prepare(C)
     seed = prep["seed"]
     S = {"seed": seed, "spec": spec, "dims": (B, H, Lq, Lk, dh), "strides": strides, "scale": scale}
-    if C.cd == torch.bfloat16 and C.attn_impl == "fused" and dh in (32, 64) and not _keys_need_unfused(spec, Lq, Lk, dh):
+    if C.cd == torch.bfloat16 and C.attn_impl == "fused" and dh in (32, 64):
         dm, ready = prep["dropmask"], prep["ready"]
         if not ready:
             dm = K.dropmask_buffer(B, H, Lq, Lk, dh, C.p, q.device)
@@ -446,16 +426,13 @@ def ffn_core_bwd(C, w, x, f, fb, dy_c, sink, dx_dtype, dres=None, wcast=_resolve
     return dx, grads
 
 
-def ln_fwd_attn(C, x, ln, prep, B, H, Lq, Lk, dh, spec=None):
+def ln_fwd_attn(C, x, ln, prep, B, H, Lq, Lk, dh):
     """The sublayer's LayerNorm; where the fused attention will take dropout keep bits, they are generated in the
-    same launch (asrx_layernorm_fwd_attn_dropgen) and handed to the attention through prep.  spec: the attention's
-    mask, where it can send the attention to the materialised-scores program (_keys_need_unfused), which draws its
-    dropout in the row softmax and takes no keep bits."""
+    same launch (asrx_layernorm_fwd_attn_dropgen) and handed to the attention through prep."""
     d = x.shape[1]
     dm = (K.dropmask_buffer(B, H, Lq, Lk, dh, C.p, x.device)
           if prep["dropmask"] is None and C.cd == torch.bfloat16 and C.attn_impl == "fused"
-          and d == 512 and x.dtype == torch.float32 and not (spec is not None and _keys_need_unfused(spec, Lq, Lk, dh))
-          else None)
+          and d == 512 and x.dtype == torch.float32 else None)
     if dm is None:
         return ln_fwd(C, x, ln)
     h = _empty(x.shape, C.cd, x)
@@ -479,7 +456,7 @@ def self_attn_fwd(C, x, ln, mha, B, T, H, spec):
     """x + Drop(MHA(LN(x))) with fused per-head projections (layers.py:10-12 -> one N=3d GEMM)."""
     dh = x.shape[1] // H
     prep = attn_prepare(C)
-    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, T, T, dh, spec)
+    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, T, T, dh)
     w = (C.W(mha.wqkv), mha.bqkv.data, None, None, C.W(mha._out_linear.weight), mha._out_linear.bias.data)
     y, S = attn_core_fwd(C, w, h, B, H, dh, T, T, spec, resid=x, prep=prep)
     S.update(x=x, mean=mean, rstd=rstd, ln=ln, mha=mha)
@@ -507,7 +484,7 @@ def cross_attn_fwd(C, x, ln, mha, kv, kv_ld, B, L, Te, H, group=1, spec=None):
         B, L = B // group, L * group
     dh = x.shape[1] // H
     prep = attn_prepare(C)
-    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, L, Te, dh, spec)
+    h, mean, rstd = ln_fwd_attn(C, x, ln, prep, B, H, L, Te, dh)
     w = (C.W(mha.wq), mha.bq.data, None, None, C.W(mha._out_linear.weight), mha._out_linear.bias.data)
     y, S = attn_core_fwd(C, w, h, B, H, dh, L, Te, spec or MaskSpec(), kv=kv, resid=x, prep=prep)
     S.update(x=x, mean=mean, rstd=rstd, ln=ln, mha=mha)

@@ -949,7 +949,9 @@ def step_tokens(text, inp, mask):
 def length_mask(lengths, T, subsample=0, enc_len=None, valid=None):
     """(enc_len int32 [B], valid uint8 [B, T]) of int32 device lengths [B] in one launch (asrx_length_mask, DESIGN.md
     §18): enc_len = clamp(the k3/s2 length arithmetic applied `subsample` times, 0, T), valid[b, t] = t < enc_len[b].
-    enc_len / valid: buffers to write into (a captured step's) instead of fresh ones."""
+    enc_len / valid: buffers to write into (a captured step's) instead of fresh ones.  A fresh valid has rows
+    ceil4(T) bytes apart: the streamed attention forward takes key-validity rows only on 4-byte boundaries (a caller's
+    own rows at another stride or base get the kernels that read bytes, csrc/attention.hip stream_ok)."""
     _cuda(lengths, enc_len, valid)
     if lengths.dtype != torch.int32 or lengths.dim() != 1 or not lengths.is_contiguous():
         raise ValueError(f"asrx: lengths must be a contiguous int32 vector, got {lengths.dtype} {tuple(lengths.shape)}")
@@ -957,7 +959,7 @@ def length_mask(lengths, T, subsample=0, enc_len=None, valid=None):
     if enc_len is None:
         enc_len = torch.empty(B, dtype=torch.int32, device=lengths.device)
     if valid is None:
-        valid = torch.empty(B, T, dtype=torch.uint8, device=lengths.device)
+        valid = torch.empty(B, (T + 3) // 4 * 4, dtype=torch.uint8, device=lengths.device)[:, :T]
     assert enc_len.dtype == torch.int32 and enc_len.is_contiguous() and enc_len.numel() == B
     assert valid.dtype == torch.uint8 and valid.shape == (B, T) and valid.stride(1) == 1 and valid.stride(0) >= T
     call("asrx_length_mask", lengths.data_ptr(), B, T, int(subsample), enc_len.data_ptr(), valid.data_ptr(),

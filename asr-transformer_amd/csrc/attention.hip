@@ -819,12 +819,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void a
       // lazy rescale (wave-uniform): the rows' reference maxima move only when some row's max grew by more than
       // 2^8; in between, probabilities up to 2^8 accumulate against the stale reference (exact algebra, fp32 sums;
       // round 6: the exact rescale ran on almost every tile of random scores, ~40 of the tile's ~190 VALU)
+      // MODE 1: only the rows that crossed the threshold move (alpha is exactly 1 for the others), so a row's bits
+      // depend on no other row of its wave — a dead query's garbage must not reach its live neighbours
       if (__ballot(m_new - m_run[qs] > kLazy)) {
-        const float alpha = exp2_raw(m_run[qs] - (m_new == -INFINITY ? 0.f : m_new));
+        const float m_to = (MODE == 1 && !(m_new - m_run[qs] > kLazy)) ? m_run[qs] : m_new;
+        const float alpha = exp2_raw(m_run[qs] - (m_to == -INFINITY ? 0.f : m_to));
         l_run[qs] *= alpha;
 #pragma unroll
         for (int u = 0; u < 4; ++u) o[u][qs] *= alpha;
-        m_run[qs] = m_new;
+        m_run[qs] = m_to;
       }
       const float m_use = m_run[qs] == -INFINITY ? 0.f : m_run[qs];
       float rs = -0.f;   // (x + -0 = x exactly: the first add folds away)
@@ -1176,7 +1179,11 @@ void attn_fwd_stream_kernel(AttnArgs a, const uint32_t* qmaj) {
       wvo[i] = (uint32_t)((min(qw0 + ((i * 64 + l) >> 2), a.Lq - 1) * qst + (l & 3)) * 4);
   }
   const bool kvm = MODE == 1 && a.kvalid;
-  if (kvm) msrd = asrxg::make_srd(a.kvalid + b * a.validb, a.Lk);
+  // The validity bytes move as 4-byte words, so the range ends with the word that holds byte Lk - 1: a range of Lk
+  // bytes clips that word whole when Lk % 4 != 0 (its keys then read as invalid).  The row base is word-aligned
+  // (stream_ok), so the up to 3 bytes read past the row lie in the aligned word of byte Lk - 1 — the same page —
+  // and are never looked at: keys >= Lk are refused by index below.
+  if (kvm) msrd = asrxg::make_srd(a.kvalid + b * a.validb, ((int64_t)a.Lk + 3) & ~(int64_t)3);
   uint64_t t_start = 0, t_staged = 0;   // per-block real-time stamps (ASRX_ATTN_DBG=1, tools/attn_bench.py --dbg)
   if (kStamps && a.dbg) t_start = __builtin_amdgcn_s_memrealtime();
   constexpr int NC = 4 + (DROP ? 2 : 0) + (MODE == 1 ? 1 : 0);   // vector-memory ops per chunk and wave
@@ -1293,11 +1300,12 @@ void attn_fwd_stream_kernel(AttnArgs a, const uint32_t* qmaj) {
             }
           } else {
             if (__ballot((m_new - m_run[qs]) * sc2 > kLazy)) {   // lazy rescale (see attn_fwd_res_kernel)
-              const float alpha = exp2_raw((m_run[qs] - (m_new == -INFINITY ? 0.f : m_new)) * sc2);
+              const float m_to = (MODE == 1 && !((m_new - m_run[qs]) * sc2 > kLazy)) ? m_run[qs] : m_new;
+              const float alpha = exp2_raw((m_run[qs] - (m_to == -INFINITY ? 0.f : m_to)) * sc2);
               l_run[qs] *= alpha;
 #pragma unroll
               for (int u = 0; u < 4; ++u) o[u][qs] *= alpha;
-              m_run[qs] = m_new;
+              m_run[qs] = m_to;
             }
             m_use = m_run[qs] == -INFINITY ? 0.f : m_run[qs];
           }
@@ -1874,6 +1882,10 @@ bool resident_ok(const asrx_attn_desc* d, const AttnArgs& a) {
 bool stream_ok(const asrx_attn_desc* d, const AttnArgs& a, bool any_lk = false) {
   if (force_tiled()) return false;
   if (d->dh != 64 || (a.Lk <= R_MAXK && !any_lk) || a.mode == 2) return false;
+  // the streamed forward moves each row of key-validity bytes as 4-byte words: every row base on a word boundary,
+  // else the kernels that read the bytes one by one (resident up to R_MAXK keys, tiled past that; the backward
+  // follows the forward, whose keep words it shares)
+  if (a.mode == 1 && a.kvalid && (((uintptr_t)a.kvalid | (uintptr_t)a.validb) % 4)) return false;
   constexpr int64_t L24 = 1 << 23, L31 = (int64_t)1 << 31;
   const bool s24 = a.qr < L24 && a.orr < L24 && a.Lq < L24 && (!a.dout || (a.dor < L24 && a.dqr < L24));
   const int64_t qs = std::max({(int64_t)a.qr, (int64_t)a.orr, a.dout ? (int64_t)a.dor : 0, a.dout ? (int64_t)a.dqr : 0});

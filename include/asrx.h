@@ -194,6 +194,9 @@ int asrx_set_tuning(int32_t key, int32_t value);
  * mask_mode: 0 none (encoder self / cross, model.py:21,71);
  *            1 structured: causal (if causal) OR key invalid (kvalid[b*valid_bstride+key]==0) OR query
  *              invalid (qvalid[...]==0) — the decoder mask of model.py:108-115 without materialising it;
+ *              any lk, valid_bstride >= lk and kvalid address give the same result: rows on 4-byte boundaries
+ *              (kvalid % 4 == 0, valid_bstride % 4 == 0) may take the streamed kernels, which read up to 3 bytes
+ *              past byte lk - 1 inside its aligned word and ignore them; other rows are read byte by byte;
  *            2 dense bytes: masked where mask[b*mask_sb + q*mask_sq + key*mask_sk] != 0 (layers.py:22-23).
  * Replaces MHAHead.forward's bmm/mul/masked_fill/softmax/nan_to_num/dropout/bmm (layers.py:20-27).
  * Supported dh: 32, 64.

@@ -30,6 +30,10 @@ Forward kernels asrx_attention_fwd can launch, and the cases (B = H = 2, dh = 64
   attn_fwd_stream_kernel<0, true>   auto  none   (57,1031) (300,300) dropout
   attn_fwd_stream_kernel<1, false>  auto  decoder (300,300); causal / key / query validity cases at 300
   attn_fwd_stream_kernel<1, true>   auto  decoder (300,300) dropout (the exact-rescale copy)
+  (mode 1 here has L = 300, a multiple of 4, Lq == Lk and validity rows L bytes apart.  Key-only masks with Lq != Lk,
+   key counts that are no multiple of 4 on either side of 256, validity rows at other strides and bases, and the
+   backward under a key-only mask — res<1>, stream<1, *>, bwd_res<1, 8> and <1, 8, true>, the tiled pair — are
+   tests/test_gpu_attention_keymask.py's, with this file's Ref, check_fwd, run_fwd / run_bwd and bounds)
   attn_fwd_kernel<64>               tiled none (64,249) (300,300); dropout without keep words; auto dense (300,300)
   attn_fwd_kernel<32>               auto  none (64,249) dh = 32
 Backward kernels asrx_attention_bwd can launch (shared_top; ramp_big at (300,300)):

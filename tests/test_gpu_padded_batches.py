@@ -5,17 +5,19 @@ Model: d 512, 8 heads (dh 64: the fused kernels), 2 + 2 layers, vocab 250, L = 1
 (spectrogram frames -> encoder frames T'), and the program each masked bf16 attention takes (fp32 always takes the
 materialised-scores program with asrx_softmax_fwd mode 1):
   G1  T   64: 64, 40, 23     -> 15, 9, 5       encoder and cross-attention: resident forward / backward <1>
-  G2  T  600: 600, 333, 130  -> 149, 82, 31    T' % 4 = 1, where the encoder's attention would stream: the guard
-                                               (blocks._keys_need_unfused) sends it to the materialised-scores program;
+  G2  T  600: 600, 333, 130  -> 149, 82, 31    T' % 4 = 1: the encoder on attn_fwd_stream_kernel<1> (two chunks) and
+                                               attn_bwd_res_kernel<1, 8>, the last validity word partial;
                                                cross-attention (16 queries): resident <1>
-  G3  T 1100: 1100, 700, 130 -> 274, 174, 31   T' % 4 = 2, T' > 256: encoder and cross-attention both guarded
+  G3  T 1100: 1100, 700, 130 -> 274, 174, 31   T' % 4 = 2, T' > 256: encoder and cross-attention on
+                                               attn_fwd_stream_kernel<1>, the key-block backward <1, 8, true>
   G4  T  611: 611, 333, 130  -> 152, 82, 31    T' % 4 = 0: the encoder on attn_fwd_stream_kernel<1> at 128 < Lk <= 256
                                                and attn_bwd_res_kernel<1, 8>; two utterances leave whole 32-key tiles
                                                dead; cross-attention: resident <1>
   G5  T 1107: 1107, 700, 130 -> 276, 174, 31   T' % 4 = 0, T' > 256: encoder and cross-attention on
                                                attn_fwd_stream_kernel<1>, the key-block backward <1, 8, true> with the
                                                second 256-key block wholly dead for two utterances
-G1 - G3 are the issue's; G4 and G5 are what keeps the streamed kernels' key masks under test beside the guard.
+G1 - G3 are the issue's.  G2 and G3 took the materialised-scores program while the streamed kernel clipped the last
+validity word; kernels.length_mask's rows are a multiple of 4 bytes apart, so all five stream now.
 The padding is 10 * N(0, 1).  Bounds: fp32 relerr < 1e-3 (test_forward_c2_fp32_vs_oracle's); bf16 relerr <= BF16_FACTOR
 x the oracle's own bf16-autocast error (the first rule of tests/bf16_check.py; 48 positions cannot carry its argmax
 rule); gradients by test_train_grads_micro's procedure and fp32 bound; independence of the padding bit for bit."""
@@ -173,9 +175,10 @@ def test_logits_vs_oracle_of_each_utterance_alone(geo, precision):
 def test_encoder_rows_vs_oracle_of_each_utterance_alone(geo, precision):
     """Encoder.forward(x, input_lengths=): its valid rows, stacked, against the oracle's encoder outputs.  G2 (149 rows)
     and G3 (274) are no multiples of 4: the full-length utterance pins the last Lk % 4 keys, which the streamed kernel's
-    word-wise read of the validity bytes would drop (blocks._keys_need_unfused); with them dropped G3-bf16 read 4.57e-03
-    against its bound of 4.17e-03.  G4 (152) and G5 (276) are multiples of 4 and stay on the streamed kernel: the same
-    check of its own key mask, with whole 32-key tiles and a whole 256-key block dead."""
+    word-wise read of the validity bytes once dropped (the word that holds byte Lk - 1 was clipped by the descriptor's
+    range; tests/test_gpu_attention_keymask.py holds the kernel itself to that); with them dropped G3-bf16 read 4.57e-03
+    against its bound of 4.17e-03.  G4 (152) and G5 (276) are multiples of 4: the same check of the key mask with whole
+    32-key tiles and a whole 256-key block dead."""
     m = build(precision).eval()
     junk, _, t, k = batch(geo)
     el = enc_lens(geo)

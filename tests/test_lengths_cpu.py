@@ -91,37 +91,3 @@ def test_mask_spec_keys():
     valid = torch.ones(3, 40, dtype=torch.uint8)[:, :33]
     s = MaskSpec.keys(valid)
     assert (s.mode, s.causal, s.qvalid, s.valid_bstride) == (1, False, None, 40) and s.kvalid is valid
-
-
-def test_unaligned_streamed_key_masks_take_the_unfused_program():
-    """blocks._keys_need_unfused: only a key-only spec, only where the fused forward would stream K/V, only at a key
-    count that is no multiple of 4 (the streamed kernel reads the validity bytes as 4-byte words within Lk bytes)."""
-    from asrx.blocks import _keys_need_unfused as need
-    from asrx.kernels import MaskSpec
-    keys = MaskSpec.keys(torch.ones(2, 300, dtype=torch.uint8))
-    assert need(keys, 274, 274, 64) and need(keys, 149, 149, 64) and need(keys, 128, 274, 64)
-    assert not need(keys, 272, 272, 64) and not need(keys, 148, 148, 64)      # multiples of 4
-    assert not need(keys, 127, 127, 64) and not need(keys, 64, 249, 64)       # resident kernels read bytes
-    assert need(keys, 65, 249, 64) and not need(keys, 274, 274, 32)
-    valid = torch.ones(2, 274, dtype=torch.uint8)
-    assert not need(MaskSpec(), 274, 274, 64) and not need(MaskSpec(1, True, valid, valid, 274), 274, 274, 64)
-    # a row stride of the validity bytes off the word boundary: the rows' bases are no words' either
-    odd = MaskSpec.keys(torch.ones(2, 302, dtype=torch.uint8)[:, :276])
-    assert need(odd, 276, 276, 64) and need(odd, 152, 152, 64) and not need(odd, 64, 152, 64)
-    assert not need(MaskSpec.keys(torch.ones(2, 276, dtype=torch.uint8)), 276, 276, 64)
-
-
-def test_guard_states_the_dispatchers_streaming_thresholds():
-    """blocks.STREAM_* restate, in Python, where asrx_attention_fwd streams K/V (csrc/attention.hip); the guard above
-    protects only while they agree, so this reads the dispatcher's source and fails when either side moves."""
-    import os
-    import re
-    from asrx import blocks
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(repo, "asr-transformer_amd", "csrc", "attention.hip")).read()
-    assert int(re.search(r"constexpr int R_MAXK = (\d+);", src).group(1)) == blocks.STREAM_ABOVE_LK
-    take = re.search(r"const bool take_stream = .*?a\.Lk > (\d+) && a\.Lk <= R_MAXK && a\.Lq > (\d+) &&\s*"
-                     r"stream_ok\(d, a, true\);", src, re.S)
-    assert take and (int(take.group(1)), int(take.group(2))) == (blocks.STREAM_FROM_LK, blocks.STREAM_FROM_LQ)
-    # past R_MAXK the only way to the streamed kernel is stream_ok, which refuses every Lk <= R_MAXK
-    assert re.search(r"if \(d->dh != 64 \|\| \(a\.Lk <= R_MAXK && !any_lk\) \|\| a\.mode == 2\) return false;", src)
