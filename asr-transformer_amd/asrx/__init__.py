@@ -5,7 +5,7 @@ library libasrx.so (hand-written HIP/CDNA4 kernels).  There is no CPU fallback: 
 native library and a GPU.
 """
 from .layers import MHA, FeedForward, LayerNorm, TrainablePositionalEncoding  # noqa: F401
-from .functions import BeamResult, RescoreResult  # noqa: F401
+from .decode import BeamResult, CtcInput, RescoreResult  # noqa: F401
 from .kernels import CtcAlignment  # noqa: F401
 from .augment import SpecAugment  # noqa: F401
 from .ctc import CTCLoss  # noqa: F401

@@ -204,25 +204,25 @@ class Decoder(nn.Module):
 
     def evaluate(self, x, enc_x, enc_lengths=None):
         """enc_lengths: as in forward."""
-        from .functions import decoder_evaluate
+        from .decode import decoder_evaluate
         return decoder_evaluate(self, x, enc_x, enc_lengths)
 
     def beam_search(self, x, enc_x, beam=4, max_len=None, length_penalty=0.0, final_norm=True, nbest=1, poll=8,
                     ctc=None, ctc_weight=0.0, lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
-        """Beam-search decoding (no reference counterpart; see functions.decoder_beam_search) -> BeamResult.
+        """Beam-search decoding (no reference counterpart; see decode.decoder_beam_search) -> BeamResult.
         lm / lm_weight / token_bonus: shallow fusion with an asrx.NgramLM on the device.  enc_lengths: as in forward."""
-        from .functions import decoder_beam_search
+        from .decode import decoder_beam_search
         return decoder_beam_search(self, x, enc_x, beam, max_len, length_penalty, final_norm, nbest, poll, ctc,
                                    ctc_weight, lm, lm_weight, token_bonus, enc_lengths)
 
     def rescore(self, enc_x, ctc, beam=8, ctc_weight=0.5, nbest=1, final_norm=True, max_len=None, mbr_scale=None,
                 lm=None, lm_weight=0.0, token_bonus=0.0, enc_lengths=None):
         """Two-pass decoding from an encoder output and its CTC logits, ctc = (logits, T, blank, input_lengths) as in
-        beam_search (no reference counterpart; see functions.decoder_rescore) -> RescoreResult.  mbr_scale: a number
+        beam_search (no reference counterpart; see decode.decoder_rescore) -> RescoreResult.  mbr_scale: a number
         orders the hypotheses by minimum Bayes risk under softmax(mbr_scale * score) and fills `risks`.  lm (an
         asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank and
         fills `lm_scores`.  enc_lengths: as in forward, for the second pass's cross-attention."""
-        from .functions import decoder_rescore
+        from .decode import decoder_rescore
         return decoder_rescore(self, enc_x, ctc, beam, ctc_weight, nbest, final_norm, max_len, mbr_scale, lm,
                                lm_weight, token_bonus, enc_lengths)
 
@@ -274,7 +274,7 @@ class Transformer(nn.Module):
 
     def evaluate(self, spectrum, text, input_lengths=None):
         """input_lengths: as in forward."""
-        from .functions import transformer_evaluate
+        from .decode import transformer_evaluate
         return transformer_evaluate(self, spectrum, text, input_lengths)
 
     def beam_search(self, spectrum, text=None, ctc_weight=0.0, input_lengths=None, **kw):
@@ -284,13 +284,13 @@ class Transformer(nn.Module):
         mask_padding they also mask the padded frames in the encoder and the cross-attention, at any ctc_weight).
         lm=, lm_weight=, token_bonus= (an asrx.NgramLM on the device): shallow fusion, every generated token also
         earns lm_weight * log p_lm + token_bonus; lm=None or lm_weight=0 is the search without an LM."""
-        from .functions import transformer_beam_search
+        from .decode import transformer_beam_search
         return transformer_beam_search(self, spectrum, text, ctc_weight, input_lengths, **kw)
 
     def ctc_logits(self, spectrum, input_lengths=None):
         """Front end, encoder and the CTC head (ctc=True models), no grad: fp32 logits (B, T', V).  input_lengths: as
         in forward (the rows behind them are then unspecified)."""
-        from .functions import transformer_ctc_logits
+        from .decode import transformer_ctc_logits
         logits, B, T = transformer_ctc_logits(self, spectrum, input_lengths)
         return logits.view(B, T, -1)[:, :, :self.ctc_head.V]
 
@@ -298,7 +298,7 @@ class Transformer(nn.Module):
         """CTC best-path transcript without the decoder: per frame the arg-max of ctc_logits, repeats collapsed,
         blanks removed, on the device.  input_lengths: (B,) valid encoder frames (None: all T').  Returns (tokens
         (B, T') int64 left-packed and padded with the blank id, lengths (B,) int32), both on the device."""
-        from .functions import transformer_ctc_greedy
+        from .decode import transformer_ctc_greedy
         return transformer_ctc_greedy(self, spectrum, input_lengths)
 
     def align(self, spectrum, text, mask=None, input_lengths=None):
@@ -311,7 +311,7 @@ class Transformer(nn.Module):
         per-label confidence, score (B,) fp32 log-probability of the path (-inf: the transcript cannot be aligned, for
         instance more labels than frames), and targets (B, n) int64 / target_lengths (B,) int32, which map a position
         back to its token id."""
-        from .functions import transformer_align
+        from .decode import transformer_align
         return transformer_align(self, spectrum, text, mask, input_lengths)
 
     def ctc_beam_search(self, spectrum, beam=8, input_lengths=None, nbest=1):
@@ -319,7 +319,7 @@ class Transformer(nn.Module):
         search in one launch (asrx_ctc_prefix_beam).  Returns a BeamResult: tokens (B, nbest, max_labels) int64 labels
         padded with the blank id, lengths (B, nbest) label counts, scores (B, nbest) fp32 log p_ctc, best first;
         max_labels = min(decoder seq_len, 255) - 1."""
-        from .functions import transformer_ctc_beam_search
+        from .decode import transformer_ctc_beam_search
         return transformer_ctc_beam_search(self, spectrum, beam, input_lengths, nbest)
 
     def rescore(self, spectrum, beam=8, ctc_weight=0.5, input_lengths=None, nbest=1, final_norm=True, max_len=None,
@@ -334,7 +334,7 @@ class Transformer(nn.Module):
         `beam` hypotheses (asrx_edit_distance + asrx_mbr_rank on the device) and `risks` is filled; None: as before.
         lm (an asrx.NgramLM on the device) with lm_weight > 0 adds lm_weight * log p_lm + token_bonus * len to the rank
         (asrx_ngram_seq_logprob) and fills `lm_scores`."""
-        from .functions import transformer_rescore
+        from .decode import transformer_rescore
         return transformer_rescore(self, spectrum, beam, ctc_weight, input_lengths, nbest, final_norm, max_len,
                                    mbr_scale, lm, lm_weight, token_bonus)
 

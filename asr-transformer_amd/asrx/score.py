@@ -10,7 +10,7 @@ from typing import NamedTuple
 import torch
 
 from . import kernels as K
-from .functions import BeamResult, RescoreResult
+from .decode import BeamResult, RescoreResult, check_mbr_scale
 
 
 class EditCounts(NamedTuple):
@@ -188,13 +188,6 @@ class ErrorRate:
             host.append((flat[o:o + B * W].view(B, W), flat[o + B * W:o + 5 * B * W].view(B, W, 4)))
             o += 5 * B * W
         return reduce_counts(host)
-
-
-def check_mbr_scale(scale):
-    scale = float(scale)
-    if scale != scale or scale < 0.0:
-        raise ValueError(f"mbr_scale {scale} must be >= 0")
-    return scale
 
 
 @torch.no_grad()

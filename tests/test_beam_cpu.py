@@ -56,7 +56,7 @@ def test_empty_calls_succeed_without_gpu():
 def test_backtrack_hand_written_history():
     """Three steps, W = 3, one sample.  Step 0: all from slot 0 with tokens 7 8 9.  Step 1: slots extend (1, 0, 1)
     with 5 6 4.  Step 2: slots extend (2, 2, 0) with 3 2 1."""
-    from asrx.functions import beam_backtrack
+    from asrx.decode import beam_backtrack
     parents = torch.tensor([[[0, 0, 0]], [[1, 0, 1]], [[2, 2, 0]]], dtype=torch.int32)
     toks = torch.tensor([[[7, 8, 9]], [[5, 6, 4]], [[3, 2, 1]]])
     seqs = beam_backtrack(parents, toks)
@@ -71,7 +71,7 @@ def test_backtrack_hand_written_history():
 
 
 def test_rank_orders_by_normalised_score_and_puts_dead_last():
-    from asrx.functions import beam_rank
+    from asrx.decode import beam_rank
     inf = float("inf")
     score = torch.tensor([[-4.0, -inf, -3.0, -6.0]])
     length = torch.tensor([[2, 1, 1, 4]])

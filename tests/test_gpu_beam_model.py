@@ -106,7 +106,7 @@ def test_beam_search_nbest_and_length_penalty():
 def test_beam_one_without_final_norm_is_greedy_evaluate(precision, prefix):
     """beam = 1, final_norm = False, no length penalty: the last sample's tokens are those of the cached greedy
     decode (`evaluate`) up to and including its first generated EOS, and EOS from there on."""
-    from asrx.functions import _decoder_evaluate_cached
+    from asrx.decode import _decoder_evaluate_cached
     cfg = CONFIGS["c1"]["cfg"]
     m = build(det_params(cfg, 3), cfg, precision)
     g = torch.Generator().manual_seed(5)

@@ -342,7 +342,7 @@ def test_score_joint_step_advance_end_to_end(T, V, ld, W, B, lam, seed):
     for s, (p, t, _, _) in enumerate(ref["history"]):
         assert torch.equal(par[s].cpu().long(), p), f"parents of step {s}"
         assert torch.equal(tok[s].cpu(), t), f"tokens of step {s}"
-    from asrx.functions import beam_backtrack
+    from asrx.decode import beam_backtrack
     seqs = beam_backtrack(par.cpu().view(E2E_STEPS, B, W), tok.cpu().view(E2E_STEPS, B, W))
     assert torch.equal(seqs, ref["tokens"])
     got = state[0].cpu().double().view(B, W)

@@ -179,10 +179,10 @@ def test_greedy_decode_c1(golden_dir):
 @pytest.mark.parametrize("prefix", [1, 3])
 def test_greedy_decode_cache_equals_recompute(precision, prefix):
     """The KV-cached batched decode (eval) returns what the reference's per-sample full-prefix recomputation
-    returns (model.py:125-151, restated as functions._decoder_evaluate_recompute): the same last-sample token row,
+    returns (model.py:125-151, restated as decode._decoder_evaluate_recompute): the same last-sample token row,
     the same number of EOS/final-step logits snapshots, each of the same shape and value; also with a multi-token
     prompt (prefill through the cache)."""
-    from asrx.functions import _decoder_evaluate_cached, _decoder_evaluate_recompute
+    from asrx.decode import _decoder_evaluate_cached, _decoder_evaluate_recompute
     m, cfg = build("c1", precision, seed=3)
     m.eval()
     g = torch.Generator().manual_seed(5)

@@ -21,7 +21,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "asr-transformer_amd")]
 import torch  # noqa: E402
 
 import asrx  # noqa: E402
-from asrx.functions import _decoder_evaluate_cached  # noqa: E402
+from asrx.decode import _decoder_evaluate_cached  # noqa: E402
 from oracle.ref_model import CONFIGS  # noqa: E402
 
 

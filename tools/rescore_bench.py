@@ -28,7 +28,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "asr-transformer_amd")]
 import torch  # noqa: E402
 
 import asrx  # noqa: E402
-from asrx import functions as Fn  # noqa: E402
+from asrx import decode  # noqa: E402
 from asrx import kernels as K  # noqa: E402
 from oracle.ref_model import CONFIGS  # noqa: E402
 from tools.joint_bench import head_logits, summary, timed  # noqa: E402
@@ -72,7 +72,7 @@ def main():
     variants = {
         "joint": lambda: dec.beam_search(bos, enc, beam=W, max_len=a.steps, poll=0, ctc=ctc, ctc_weight=0.3),
         "rescore": lambda: dec.rescore(enc, ctc, beam=W, max_len=a.steps),
-        "ctc_beam": lambda: Fn.decoder_ctc_beam_search(dec, ctc, a.batch, beam=W, max_len=a.steps),
+        "ctc_beam": lambda: decode.decoder_ctc_beam_search(dec, ctc, a.batch, beam=W, max_len=a.steps),
     }
     times = {k: [] for k in variants}
     with torch.no_grad():
