@@ -1780,6 +1780,14 @@ extern "C" int asrx_gemm(const asrx_gemm_desc* d, void* stream) {
     const GemmPlan pl = plan_bf16(d, batch, g.splitk);
     g.cvec = pl.cvec;
     reduce = pl.reduce;
+    // Splits without a K range (k_per_split is rounded up to whole K-steps, so the trailing ones can be empty): the
+    // register and ring kernels store zero partials for them, p3 leaves such a split's slab and row-sum row
+    // unwritten.  p3 therefore launches and reduces only the splits that have a range — the same sum, as the others
+    // would add zeros; a single one runs unsplit, through the generic epilogue the split plan carries.
+    if (pl.family == Family::P3 && g.splitk > 1 && g.k_per_split > 0) {
+      g.splitk = std::max(1, (g.K + g.k_per_split - 1) / g.k_per_split);
+      if (g.splitk == 1) reduce = Reduce::None;
+    }
     rc = launch_plan(d, g, pl, batch, st);
     if (rc != ASRX_OK) return rc;
   } else {

@@ -60,7 +60,11 @@ int asrx_struct_sizes(int64_t* out, int32_t n);
  *              (z*M + m)*N + n) -> *gate (keep where gate[m][n] > 0) -> +resid[m][n] -> +beta*C_old -> store
  * Replaces: nn.Linear (layers.py:10-12,36,48,51; model.py:32,102) = aten::addmm/linear, the per-head
  * q@k^T and attn@v aten::bmm (layers.py:20,27), and the conv2 implicit GEMM (model.py:168-171).
- * Split-K (splitk > 1, batch == 1) needs workspace of splitk*M*N floats (reduced in fixed split order).
+ * Split-K (splitk > 1, batch == 1) needs workspace of splitk*M*N floats (reduced in fixed split order).  A split
+ * covers ceil(ceil(K / 64) / splitk) * 64 reduction elements (16-deep steps for fp32 operands), so trailing splits
+ * can be left without a K range (K = 576, splitk = 7: splits 5 and 6); they contribute zero.  The workspace (and
+ * rowsum_ws) needs no initialisation: every element the reduction reads is written by the same call, and nothing
+ * outside the first splitk*M*N (splitk*M) elements is touched.
  * ------------------------------------------------------------------------------------------------- */
 typedef struct asrx_gemm_desc {
   int32_t m, n, k;
