@@ -109,6 +109,14 @@ def kernel_name(d):
     return buf.value.decode()
 
 
+def attn_kernel_name(d, backward=False):
+    """The kernels asrx_attention_fwd (backward: asrx_attention_bwd) would enqueue for the AttnDesc d, in order, joined
+    by " + " and named as rocprofv3 lists them.  Host arithmetic on d alone; raises where the call itself would."""
+    buf = ctypes.create_string_buffer(128)
+    call("asrx_attn_kernel_name", ctypes.byref(d), int(bool(backward)), buf, 128)
+    return buf.value.decode()
+
+
 PROBE = None
 
 # asrx_gemm_desc.kernel: forced kernel family (0 = auto).  ASRX_GEMM_KERNEL picks a process-wide default (A/B).

@@ -1854,51 +1854,281 @@ int fill_args(const asrx_attn_desc* d, AttnArgs& a) {
   return ASRX_OK;
 }
 
-// ASRX_ATTN_KERNEL=tiled forces the general tiled kernels (read per call: the tests switch it between cases)
-bool force_tiled() {
-  const char* e = getenv("ASRX_ATTN_KERNEL");
-  return e && !strcmp(e, "tiled");
-}
-
-// Lk <= 256 and dh = 64 -> resident-K/V kernels
-bool resident_ok(const asrx_attn_desc* d, const AttnArgs& a) {
-  if (force_tiled()) return false;
-  // row offsets inside the resident kernels are 24-bit products (q * row stride): strides and lengths < 2^23
-  constexpr int64_t L24 = 1 << 23;
-  const bool s24 = a.qr < L24 && a.kr < L24 && a.vr < L24 && a.orr < L24 && a.Lq < L24 && a.Lk < L24 &&
-                   (!a.dout || (a.dor < L24 && a.dqr < L24 && a.dkr < L24 && a.dvr < L24));
-  // ... and the products themselves are 32-bit int offsets: every row index times its stride < 2^31
-  constexpr int64_t L31 = (int64_t)1 << 31;
-  const int64_t qs = std::max({(int64_t)a.qr, (int64_t)a.orr, a.dout ? (int64_t)a.dor : 0, a.dout ? (int64_t)a.dqr : 0});
-  const int64_t ks = std::max({(int64_t)a.kr, (int64_t)a.vr, a.dout ? (int64_t)a.dkr : 0, a.dout ? (int64_t)a.dvr : 0});
-  // (the backward's dQ stores address rows up to Lq + 31, dropped by the descriptor's range: still 32-bit)
-  const bool s31 = ((int64_t)a.Lq + 32) * qs < L31 && (int64_t)a.Lk * ks < L31;
-  return d->dh == 64 && a.Lk <= R_MAXK && (a.orr % 4) == 0 && (a.ob % 4) == 0 && s24 && s31;
-}
-
-// Lk > 256, dh = 64, no mask or the structured mask -> the streamed forward / key-block backward
-// (ASRX_ATTN_KERNEL=tiled: the general tiled kernels): 16-B aligned K/V rows for the LDS-DMA, 32-bit byte offsets of every K/V row of the padded last chunk,
-// and the backward's 24-bit query-row products
-bool stream_ok(const asrx_attn_desc* d, const AttnArgs& a, bool any_lk = false) {
-  if (force_tiled()) return false;
-  if (d->dh != 64 || (a.Lk <= R_MAXK && !any_lk) || a.mode == 2) return false;
-  // the streamed forward moves each row of key-validity bytes as 4-byte words: every row base on a word boundary,
-  // else the kernels that read the bytes one by one (resident up to R_MAXK keys, tiled past that; the backward
-  // follows the forward, whose keep words it shares)
-  if (a.mode == 1 && a.kvalid && (((uintptr_t)a.kvalid | (uintptr_t)a.validb) % 4)) return false;
-  constexpr int64_t L24 = 1 << 23, L31 = (int64_t)1 << 31;
-  const bool s24 = a.qr < L24 && a.orr < L24 && a.Lq < L24 && (!a.dout || (a.dor < L24 && a.dqr < L24));
-  const int64_t qs = std::max({(int64_t)a.qr, (int64_t)a.orr, a.dout ? (int64_t)a.dor : 0, a.dout ? (int64_t)a.dqr : 0});
-  const int64_t ks = std::max({(int64_t)a.kr, (int64_t)a.vr, a.dout ? (int64_t)a.dkr : 0, a.dout ? (int64_t)a.dvr : 0});
-  const bool s31 = ((int64_t)a.Lq + 32) * qs < L31 && ((int64_t)a.Lk + R_MAXK) * ks * 2 < L31 &&
-                   (int64_t)a.Lq * qmaj_stride(a.Lk) * 4 < L31 && ((int64_t)a.Lq + 32) * a.H * 64 * 4 < L31;
-  return a.orr % 4 == 0 && a.ob % 4 == 0 && a.kr % 8 == 0 && a.vr % 8 == 0 && ((uintptr_t)a.k % 16) == 0 &&
-         ((uintptr_t)a.v % 16) == 0 && s24 && s31;
-}
-
 size_t bwd_smem(int nw, int dh) {
   const int kst = dh + 16, cs = dh + 16, dss = 36;
   return (size_t)(32 * nw * kst + 2 * 16 * cs + nw * 16 * dss) * 2 + (size_t)nw * 16 * dh * 4 + 32 * 4;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// dispatch: plan_fwd / plan_bwd decide everything one call enqueues (AttnPlan), launch_fwd / launch_bwd enqueue it,
+// and asrx_attn_kernel_name formats the same plan (plan_name), so a test or a profile can ask which kernels run
+// ---------------------------------------------------------------------------------------------------------
+
+// ASRX_ATTN_KERNEL=tiled forces the general tiled kernels, =resident keeps 128 < Lk <= 256 off the streamed forward
+// (read once per call and not cached: the tests switch it between cases)
+enum class Forced { Auto, Tiled, Resident };
+Forced forced_kernel() {
+  const char* e = getenv("ASRX_ATTN_KERNEL");
+  if (e && !strcmp(e, "tiled")) return Forced::Tiled;
+  if (e && !strcmp(e, "resident")) return Forced::Resident;
+  return Forced::Auto;
+}
+
+// the query-major keep words of a.dropmask: they follow the key-major ones (asrx.h, asrx_attn_desc.dropmask)
+uint32_t* keep_qmaj(const AttnArgs& a) { return a.dropmask + (int64_t)a.B * a.H * ((a.Lq + 31) / 32) * a.Lk; }
+
+// Row offsets inside the fused kernels are 24-bit products (row * row stride), so strides and lengths stay below 2^23,
+// and the products themselves are 32-bit int offsets.  A backward descriptor (dout set) brings its gradients' strides
+// along: dO and dQ go with the query rows, dK and dV with the key rows.
+constexpr int64_t L24 = 1 << 23, L31 = (int64_t)1 << 31;
+struct RowBounds {
+  bool q24, k24;    // query-side / key-side row strides and row counts < 2^23
+  int64_t qs, ks;   // the largest query-side / key-side row stride
+};
+RowBounds row_bounds(const AttnArgs& a) {
+  const bool g = a.dout != nullptr;
+  const int64_t z = 0;
+  return {a.qr < L24 && a.orr < L24 && a.Lq < L24 && (!g || (a.dor < L24 && a.dqr < L24)),
+          a.kr < L24 && a.vr < L24 && a.Lk < L24 && (!g || (a.dkr < L24 && a.dvr < L24)),
+          std::max({a.qr, a.orr, g ? a.dor : z, g ? a.dqr : z}), std::max({a.kr, a.vr, g ? a.dkr : z, g ? a.dvr : z})};
+}
+
+// The resident family (resident and short-query forward, resident backward): dh = 64, up to R_MAXK keys, every K/V
+// row of a head in LDS; 8-byte O quads.
+bool resident_ok(const AttnArgs& a, int dh) {
+  const RowBounds b = row_bounds(a);
+  // (the backward's dQ stores address rows up to Lq + 31, dropped by the descriptor's range: still 32-bit)
+  return dh == 64 && a.Lk <= R_MAXK && a.orr % 4 == 0 && a.ob % 4 == 0 && b.q24 && b.k24 &&
+         ((int64_t)a.Lq + 32) * b.qs < L31 && (int64_t)a.Lk * b.ks < L31;
+}
+
+// The streamed family (streamed forward, key-block backward): dh = 64, no mask or the structured one; 16-byte aligned
+// K/V rows for the LDS-DMA; 32-bit byte offsets of every K/V row of the padded last chunk, of a query's keep words and
+// of the dQ partials.
+bool stream_ok(const AttnArgs& a, int dh) {
+  if (dh != 64 || a.mode == 2) return false;
+  // the streamed forward moves each row of key-validity bytes as 4-byte words: every row base on a word boundary,
+  // else the kernels that read the bytes one by one (resident up to R_MAXK keys, tiled past that)
+  if (a.mode == 1 && a.kvalid && (((uintptr_t)a.kvalid | (uintptr_t)a.validb) % 4)) return false;
+  const RowBounds b = row_bounds(a);
+  return a.orr % 4 == 0 && a.ob % 4 == 0 && a.kr % 8 == 0 && a.vr % 8 == 0 && ((uintptr_t)a.k % 16) == 0 &&
+         ((uintptr_t)a.v % 16) == 0 && b.q24 && ((int64_t)a.Lq + 32) * b.qs < L31 &&
+         ((int64_t)a.Lk + R_MAXK) * b.ks * 2 < L31 && (int64_t)a.Lq * qmaj_stride(a.Lk) * 4 < L31 &&
+         ((int64_t)a.Lq + 32) * a.H * 64 * 4 < L31;
+}
+
+// Whether the fused kernels take the call: the resident family up to R_MAXK keys, the streamed one past that.
+// THE KEEP-WORD INVARIANT.  With dropout the fused kernels share their decisions as keep words: a fused forward has
+// them generated (attn_dropgen_kernel, unless the caller did: dropmask_ready) and a fused backward reads them, while
+// the tiled pair hashes the same decisions in-kernel and neither writes nor reads any.  plan_fwd and plan_bwd both
+// decide fused-or-tiled through this one predicate, and a backward descriptor only adds terms to it (row_bounds; the
+// dQ alignment in plan_bwd): wherever plan_bwd picks a kernel that reads keep words, plan_fwd on the same shapes and
+// pointers picked a path that wrote them.  tests/test_attn_plan_table.py asserts it over its whole table.
+bool fused_ok(const AttnArgs& a, int dh, Forced forced) {
+  return forced != Forced::Tiled && (!a.thr || a.dropmask) &&
+         (resident_ok(a, dh) || (a.Lk > R_MAXK && stream_ok(a, dh)));
+}
+
+// tiled: attn_fwd_kernel; resident: attn_fwd_res_kernel; short-query: attn_fwd_kq_kernel; streamed:
+// attn_fwd_stream_kernel; resident / key-block backward: attn_bwd_res_kernel (MULTI false / true); tiled backward:
+// attn_delta_kernel + attn_bwd_kernel
+enum class Family { Tiled, Resident, ShortQuery, Streamed, ResidentBwd, KeyBlockBwd, TiledBwd };
+
+// Everything one asrx_attention_fwd / asrx_attention_bwd call enqueues, or the code it returns instead.
+struct AttnPlan {
+  int err;                // ASRX_OK, else the call returns this and launches nothing
+  Family family;
+  int mode, dh, nkt;      // template arguments as launched: MODE; the tiled kernels' DH; the backward's NKT
+  bool drop, w8, multi;   // DROP (keep words in use); the resident forward's W8; the backward's MULTI
+  dim3 grid, block;
+  size_t smem;            // dynamic LDS
+  bool dropgen;           // forward: attn_dropgen_kernel first
+  const uint32_t* qmaj;   // forward: the query-major keep words (nullptr without dropout)
+  bool delta, zero_acc;   // backward: attn_delta_kernel first; dq_acc's first slab zeroed
+  int finish_parts;       // backward: dq_finish_kernel over this many dQ partials (0: no finish)
+  int nw, single;         // the tiled backward's runtime arguments
+};
+
+AttnPlan plan_error(int err) {
+  AttnPlan pl = {};
+  pl.err = err;
+  return pl;
+}
+
+AttnPlan plan_fwd(const asrx_attn_desc* d, const AttnArgs& a) {
+  if (!a.o || (a.orr % 4) || (a.ob % 4) || ((uintptr_t)a.o % 8)) return plan_error(ASRX_ERR_UNSUPPORTED);
+  const Forced forced = forced_kernel();
+  AttnPlan pl = {};
+  pl.dh = d->dh;
+  if (!fused_ok(a, d->dh, forced)) {   // any shape, mask and alignment that passed fill_args; dropout hashed in-kernel
+    pl.family = Family::Tiled;
+    pl.grid = dim3((a.Lq + 63) / 64, a.B * a.H), pl.block = dim3(256);
+    if (pl.grid.y > 65535u * 1024u) pl.err = ASRX_ERR_ARG;
+    return pl;
+  }
+  // dropout: keep bits (key-major for the backward, query-major for these kernels), generated here unless the caller
+  // already did (asrx_attn_dropgen, e.g. on a side stream while the Q/K/V projection runs)
+  pl.drop = a.thr != 0;
+  pl.dropgen = pl.drop && !d->dropmask_ready;
+  pl.qmaj = pl.drop ? keep_qmaj(a) : nullptr;
+  // 8 waves always: idle query waves still help stage K/V, then leave
+  pl.grid = dim3((a.Lq + 255) / 256, a.B * a.H), pl.block = dim3(512);
+  const bool words8 = ((a.Lk + 31) >> 5) == 8;   // a query's keep words are one 32-byte row
+  // 128 < Lk <= 256 with more than 64 queries (the c3 encoder self-attention) on the streamed forward too: its K/V
+  // arrive in two 128-key chunks, the first computed on while the second lands — in the c3 step 28.7 vs 30.3 us on
+  // the resident kernel, alone 40.4 vs 41.2 (round 4, same box)
+  const bool two_chunks = forced != Forced::Resident && a.Lk > 128 && a.Lk <= R_MAXK && a.Lq > 64 && stream_ok(a, d->dh);
+  if (a.Lk > R_MAXK || two_chunks) {
+    pl.family = Family::Streamed;
+    pl.mode = a.mode == 0 ? 0 : 1;
+  } else if (a.mode == 0 && a.Lq <= 64 && (!pl.qmaj || (words8 && (uintptr_t)pl.qmaj % 8 == 0))) {
+    // short query blocks (the decoder's cross-attention): 2 query groups x 4 key quarters per head
+    pl.family = Family::ShortQuery;
+  } else {
+    pl.family = Family::Resident;
+    pl.mode = a.mode == 0 || a.mode == 1 ? a.mode : 2;
+    pl.w8 = a.mode == 0 && pl.qmaj && words8 && (uintptr_t)pl.qmaj % 16 == 0;
+  }
+  return pl;
+}
+
+AttnPlan plan_bwd(const asrx_attn_desc* d, const AttnArgs& a) {
+  if (!a.o || !a.dout || !a.dq || !a.dk || !a.dv || !a.lse || !a.delta) return plan_error(ASRX_ERR_ARG);
+  const int64_t ostr[] = {a.orr, a.ob, a.dor, a.dob, a.dkr, a.dkb, a.dvr, a.dvb};
+  for (int64_t s : ostr) if (s % 8) return plan_error(ASRX_ERR_UNSUPPORTED);
+  AttnPlan pl = {};
+  pl.dh = d->dh;
+  // the fused backward (it forms delta itself) stores dQ as 8-byte quads.  Dropout without the keep words — a forward
+  // that took the tiled kernel — goes to the tiled backward: fused_ok
+  if (fused_ok(a, d->dh, forced_kernel()) && a.dqr % 4 == 0 && a.dqb % 4 == 0 && (uintptr_t)a.dq % 8 == 0) {
+    // (round 4's ASRX_ATTN_XSPLIT — short query blocks as two 128-key blocks of 4 waves — measured 30.8 -> 48.5 us:
+    //  removed in round 5)
+    pl.nkt = bwd_res_nkt(a.Lk);
+    const int nkb = (a.Lk + 32 * pl.nkt - 1) / (32 * pl.nkt);
+    pl.multi = nkb > 1;   // (implies nkt = 8 and Lk > R_MAXK, so mode 0 / 1 only: stream_ok)
+    pl.family = pl.multi ? Family::KeyBlockBwd : Family::ResidentBwd;
+    pl.mode = pl.multi ? (a.mode == 0 ? 0 : 1) : (a.mode == 0 || a.mode == 1 ? a.mode : 2);
+    pl.drop = a.thr != 0;
+    pl.grid = dim3(a.B * a.H, nkb), pl.block = dim3(64 * pl.nkt), pl.smem = bwd_res_smem(pl.nkt);
+    pl.finish_parts = pl.multi ? nkb : 0;             // key blocks store their dQ partials into dq_acc[blockIdx.y]
+    if (pl.multi && !a.dq_acc) pl.err = ASRX_ERR_ARG;
+    return pl;
+  }
+  pl.family = Family::TiledBwd;
+  pl.delta = true;
+  pl.nw = std::min((a.Lk + 31) / 32, 8);
+  const int nblk = (a.Lk + 32 * pl.nw - 1) / (32 * pl.nw);
+  pl.single = nblk == 1;
+  pl.zero_acc = !pl.single;                           // several key blocks add their dQ into dq_acc's first slab
+  pl.finish_parts = pl.single ? 0 : 1;
+  if (!pl.single && !a.dq_acc) pl.err = ASRX_ERR_ARG;
+  pl.grid = dim3(nblk, a.B * a.H), pl.block = dim3(64 * pl.nw), pl.smem = bwd_smem(pl.nw, d->dh);
+  return pl;
+}
+
+// The kernels launch_fwd / launch_bwd enqueue for `pl`, in order, each as rocprofv3 lists the instantiation.
+void plan_name(const AttnPlan& pl, char* buf, int len) {
+  const char* tf[2] = {"false", "true"};
+  int n = 0;
+  auto add = [&](const char* fmt, auto... v) {
+    if (n > 0 && n < len) n += snprintf(buf + n, len - n, " + ");
+    if (n < len) n += snprintf(buf + n, len - n, fmt, v...);
+  };
+  if (pl.dropgen) add("%s", "attn_dropgen_kernel");
+  if (pl.delta) add("attn_delta_kernel<%d>", pl.dh);
+  switch (pl.family) {
+    case Family::Tiled: add("attn_fwd_kernel<%d>", pl.dh); break;
+    case Family::Resident: add("attn_fwd_res_kernel<%d, %s>", pl.mode, tf[pl.w8]); break;
+    case Family::ShortQuery: add("attn_fwd_kq_kernel<%s>", tf[pl.drop]); break;
+    case Family::Streamed: add("attn_fwd_stream_kernel<%d, %s>", pl.mode, tf[pl.drop]); break;
+    case Family::ResidentBwd:
+    case Family::KeyBlockBwd: add("attn_bwd_res_kernel<%d, %d, %s>", pl.mode, pl.nkt, tf[pl.multi]); break;
+    case Family::TiledBwd: add("attn_bwd_kernel<%d>", pl.dh); break;
+  }
+  if (pl.finish_parts) add("%s", "dq_finish_kernel");
+}
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v: a plan's runtime value -> a template argument
+template <int... Vs, typename F>
+void with_int(int v, F&& f) {
+  ((v == Vs ? f(std::integral_constant<int, Vs>{}) : void()), ...);
+}
+
+int launch_dropgen(const AttnArgs& a, hipStream_t st) {
+  const int nqc = (a.Lq + 31) / 32, nkb = (a.Lk + R_MAXK - 1) / R_MAXK;
+  hipLaunchKernelGGL(attn_dropgen_kernel, dim3(nqc, a.B * a.H, nkb), dim3(256), 0, st, a, a.dropmask, keep_qmaj(a));
+  ASRX_CHECK_LAUNCH();
+  return ASRX_OK;
+}
+
+int launch_delta(const AttnArgs& a, int dh, hipStream_t st) {
+  const dim3 grid((unsigned)(((int64_t)a.B * a.H * a.Lq + 15) / 16));
+  with_int<32, 64>(dh, [&](auto DH) { hipLaunchKernelGGL(attn_delta_kernel<decltype(DH)::value>, grid, dim3(256), 0, st, a); });
+  ASRX_CHECK_LAUNCH();
+  return ASRX_OK;
+}
+
+int launch_fwd(const AttnArgs& a, const AttnPlan& pl, hipStream_t st) {
+  if (pl.dropgen) {
+    const int rc = launch_dropgen(a, st);
+    if (rc) return rc;
+  }
+  auto fused = [&](auto kernel) { hipLaunchKernelGGL(kernel, pl.grid, pl.block, 0, st, a, pl.qmaj); };
+  switch (pl.family) {
+    case Family::Tiled:
+      with_int<32, 64>(pl.dh, [&](auto DH) { hipLaunchKernelGGL(attn_fwd_kernel<decltype(DH)::value>, pl.grid, pl.block, 0, st, a); });
+      break;
+    case Family::ShortQuery:
+      if (pl.drop) fused(attn_fwd_kq_kernel<true>);
+      else fused(attn_fwd_kq_kernel<false>);
+      break;
+    case Family::Resident:
+      if (pl.w8) fused(attn_fwd_res_kernel<0, true>);
+      else with_int<0, 1, 2>(pl.mode, [&](auto M) { fused(attn_fwd_res_kernel<decltype(M)::value, false>); });
+      break;
+    case Family::Streamed:
+      with_int<0, 1>(pl.mode, [&](auto M) {
+        if (pl.drop) fused(attn_fwd_stream_kernel<decltype(M)::value, true>);
+        else fused(attn_fwd_stream_kernel<decltype(M)::value, false>);
+      });
+      break;
+    default: return ASRX_ERR_ARG;
+  }
+  ASRX_CHECK_LAUNCH();
+  return ASRX_OK;
+}
+
+int launch_bwd(const AttnArgs& a, const AttnPlan& pl, hipStream_t st) {
+  const int64_t dq_elems = (int64_t)a.B * a.Lq * a.H * pl.dh;
+  if (pl.delta) {
+    const int rc = launch_delta(a, pl.dh, st);
+    if (rc) return rc;
+  }
+  if (pl.zero_acc) hipMemsetAsync(a.dq_acc, 0, sizeof(float) * (size_t)dq_elems, st);
+  auto fused = [&](auto kernel) { hipLaunchKernelGGL(kernel, pl.grid, pl.block, pl.smem, st, a); };
+  switch (pl.family) {
+    case Family::ResidentBwd:
+      with_int<0, 1, 2>(pl.mode, [&](auto M) {
+        with_int<2, 4, 8>(pl.nkt, [&](auto N) { fused(attn_bwd_res_kernel<decltype(M)::value, decltype(N)::value, false>); });
+      });
+      break;
+    case Family::KeyBlockBwd:
+      with_int<0, 1>(pl.mode, [&](auto M) { fused(attn_bwd_res_kernel<decltype(M)::value, 8, true>); });
+      break;
+    case Family::TiledBwd:
+      with_int<32, 64>(pl.dh, [&](auto DH) {
+        hipLaunchKernelGGL(attn_bwd_kernel<decltype(DH)::value>, pl.grid, pl.block, pl.smem, st, a, pl.nw, pl.single);
+      });
+      break;
+    default: return ASRX_ERR_ARG;
+  }
+  ASRX_CHECK_LAUNCH();
+  if (pl.finish_parts) {
+    const unsigned blocks = (unsigned)std::min<int64_t>((dq_elems + 255) / 256, 8192);
+    hipLaunchKernelGGL(dq_finish_kernel, dim3(blocks), dim3(256), 0, st, a, pl.dh, pl.finish_parts);
+    ASRX_CHECK_LAUNCH();
+  }
+  return ASRX_OK;
 }
 
 }  // namespace
@@ -1922,13 +2152,7 @@ extern "C" int asrx_attn_dropgen(const asrx_attn_desc* d, void* stream) {
   if (rc) return rc;
   if (!a.dropmask) return ASRX_ERR_ARG;
   if (!a.thr) return ASRX_OK;
-  const int nqc = (a.Lq + 31) / 32, nkb = (a.Lk + R_MAXK - 1) / R_MAXK;
-  uint32_t* kmaj = a.dropmask;
-  uint32_t* qmaj = a.dropmask + (int64_t)a.B * a.H * nqc * a.Lk;
-  hipLaunchKernelGGL(attn_dropgen_kernel, dim3(nqc, a.B * a.H, nkb), dim3(256), 0, (hipStream_t)stream, a, kmaj,
-                     qmaj);
-  ASRX_CHECK_LAUNCH();
-  return ASRX_OK;
+  return launch_dropgen(a, (hipStream_t)stream);
 }
 
 extern "C" int asrx_layernorm_fwd_attn_dropgen(const float* x, void* y, const float* gamma, const float* beta,
@@ -1942,7 +2166,7 @@ extern "C" int asrx_layernorm_fwd_attn_dropgen(const float* x, void* y, const fl
   if (!a.dropmask) return ASRX_ERR_ARG;
   const int nqc = (a.Lq + 31) / 32, nkb = (a.Lk + R_MAXK - 1) / R_MAXK;
   uint32_t* kmaj = a.dropmask;
-  uint32_t* qmaj = a.dropmask + (int64_t)a.B * a.H * nqc * a.Lk;
+  uint32_t* qmaj = keep_qmaj(a);
   const int nln = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
   const int64_t ndg = a.thr ? (int64_t)nqc * a.B * a.H * nkb : 0;
   if (nln + ndg > 0x7fffffff) return ASRX_ERR_ARG;
@@ -1957,67 +2181,8 @@ extern "C" int asrx_attention_fwd(const asrx_attn_desc* d, void* stream) {
   AttnArgs a;
   int rc = fill_args(d, a);
   if (rc) return rc;
-  if (!a.o || (a.orr % 4) || (a.ob % 4) || ((uintptr_t)a.o % 8)) return ASRX_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  // 128 < Lk <= 256 with more than 64 queries (the c3 encoder self-attention) on the streamed forward too: its K/V
-  // arrive in two 128-key chunks, the first computed on while the second lands — in the c3 step 28.7 vs 30.3 us on
-  // the resident kernel, alone 40.4 vs 41.2 (round 4, same box)
-  // (ASRX_ATTN_KERNEL=resident, read per call like =tiled: the resident kernel, for tests of both paths)
-  const char* ak = getenv("ASRX_ATTN_KERNEL");
-  const bool take_stream = !(ak && !strcmp(ak, "resident")) && a.Lk > 128 && a.Lk <= R_MAXK && a.Lq > 64 &&
-                           stream_ok(d, a, true);
-  if (!take_stream && resident_ok(d, a) && (!a.thr || a.dropmask)) {
-    // dropout: keep bits (key-major for the backward, query-major for this kernel), generated here unless the
-    // caller already did (asrx_attn_dropgen, e.g. on a side stream while the Q/K/V projection runs)
-    const uint32_t* qmaj = nullptr;
-    if (a.thr) {
-      if (!d->dropmask_ready) {
-        const int rc2 = asrx_attn_dropgen(d, stream);
-        if (rc2) return rc2;
-      }
-      qmaj = a.dropmask + (int64_t)a.B * a.H * ((a.Lq + 31) / 32) * a.Lk;
-    }
-    // 8 waves always: idle query waves still help stage K/V, then leave
-    dim3 grid((a.Lq + 255) / 256, a.B * a.H);
-    const bool w8 = qmaj && ((a.Lk + 31) >> 5) == 8 && ((uintptr_t)qmaj % 16) == 0;
-    // short query blocks (the decoder's cross-attention): 2 query groups x 4 key quarters per head
-    if (a.mode == 0 && a.Lq <= 64 && (!qmaj || (((a.Lk + 31) >> 5) == 8 && (uintptr_t)qmaj % 8 == 0))) {
-      if (qmaj) hipLaunchKernelGGL((attn_fwd_kq_kernel<true>), grid, dim3(512), 0, st, a, qmaj);
-      else hipLaunchKernelGGL((attn_fwd_kq_kernel<false>), grid, dim3(512), 0, st, a, qmaj);
-      ASRX_CHECK_LAUNCH();
-      return ASRX_OK;
-    }
-    if (a.mode == 0 && w8) hipLaunchKernelGGL((attn_fwd_res_kernel<0, true>), grid, dim3(512), 0, st, a, qmaj);
-    else if (a.mode == 0) hipLaunchKernelGGL(attn_fwd_res_kernel<0>, grid, dim3(512), 0, st, a, qmaj);
-    else if (a.mode == 1) hipLaunchKernelGGL(attn_fwd_res_kernel<1>, grid, dim3(512), 0, st, a, qmaj);
-    else hipLaunchKernelGGL(attn_fwd_res_kernel<2>, grid, dim3(512), 0, st, a, qmaj);
-    ASRX_CHECK_LAUNCH();
-    return ASRX_OK;
-  }
-  if ((take_stream || stream_ok(d, a)) && (!a.thr || a.dropmask)) {   // Lk > 256: K/V streamed through LDS
-    const uint32_t* qmaj = nullptr;
-    if (a.thr) {
-      if (!d->dropmask_ready) {
-        const int rc2 = asrx_attn_dropgen(d, stream);
-        if (rc2) return rc2;
-      }
-      qmaj = a.dropmask + (int64_t)a.B * a.H * ((a.Lq + 31) / 32) * a.Lk;
-    }
-    const dim3 grid((a.Lq + 255) / 256, a.B * a.H);
-#define ASRX_STREAM(M) do { if (qmaj) hipLaunchKernelGGL((attn_fwd_stream_kernel<M, true>), grid, dim3(512), 0, st, a, qmaj); \
-                            else hipLaunchKernelGGL((attn_fwd_stream_kernel<M, false>), grid, dim3(512), 0, st, a, qmaj); } while (0)
-    if (a.mode == 0) ASRX_STREAM(0);
-    else ASRX_STREAM(1);
-#undef ASRX_STREAM
-    ASRX_CHECK_LAUNCH();
-    return ASRX_OK;
-  }
-  dim3 grid((a.Lq + 63) / 64, a.B * a.H);
-  if (grid.y > 65535u * 1024u) return ASRX_ERR_ARG;
-  if (d->dh == 64) hipLaunchKernelGGL(attn_fwd_kernel<64>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_fwd_kernel<32>, grid, dim3(256), 0, st, a);
-  ASRX_CHECK_LAUNCH();
-  return ASRX_OK;
+  const AttnPlan pl = plan_fwd(d, a);
+  return pl.err ? pl.err : launch_fwd(a, pl, (hipStream_t)stream);
 }
 
 extern "C" int asrx_attn_delta(const asrx_attn_desc* d, void* stream) {
@@ -2025,72 +2190,26 @@ extern "C" int asrx_attn_delta(const asrx_attn_desc* d, void* stream) {
   int rc = fill_args(d, a);
   if (rc) return rc;
   if (!a.o || !a.dout || !a.delta) return ASRX_ERR_ARG;
-  const int64_t rows = (int64_t)a.B * a.H * a.Lq;
-  dim3 grid((unsigned)((rows + 15) / 16));
-  hipStream_t st = (hipStream_t)stream;
-  if (d->dh == 64) hipLaunchKernelGGL(attn_delta_kernel<64>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(attn_delta_kernel<32>, grid, dim3(256), 0, st, a);
-  ASRX_CHECK_LAUNCH();
-  return ASRX_OK;
+  return launch_delta(a, d->dh, (hipStream_t)stream);
 }
 
 extern "C" int asrx_attention_bwd(const asrx_attn_desc* d, void* stream) {
   AttnArgs a;
   int rc = fill_args(d, a);
   if (rc) return rc;
-  if (!a.o || !a.dout || !a.dq || !a.dk || !a.dv || !a.lse || !a.delta) return ASRX_ERR_ARG;
-  const int64_t ostr[] = {a.orr, a.ob, a.dor, a.dob, a.dkr, a.dkb, a.dvr, a.dvb};
-  for (int64_t s : ostr) if (s % 8) return ASRX_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const bool longk = stream_ok(d, a) && (!a.thr || a.dropmask);
-  // (dropout without the keep words — a forward that took the tiled kernel — goes to the tiled backward, which hashes
-  //  the same decisions in-kernel)
-  if ((resident_ok(d, a) || longk) && (!a.thr || a.dropmask) && a.dqr % 4 == 0 && a.dqb % 4 == 0 && (uintptr_t)a.dq % 8 == 0) {   // forms delta itself
-    // (round 4's ASRX_ATTN_XSPLIT — short query blocks as two 128-key blocks of 4 waves — measured 30.8 -> 48.5 us:
-    //  removed in round 5)
-    const int nkt = bwd_res_nkt(a.Lk);
-    const int nkb = (a.Lk + 32 * nkt - 1) / (32 * nkt);
-    const size_t sm = bwd_res_smem(nkt);
-    if (nkb > 1 && !a.dq_acc) return ASRX_ERR_ARG;   // key blocks store their dQ partials into dq_acc[blockIdx.y]
-    const dim3 grid(a.B * a.H, nkb), blk(64 * nkt);
-#define ASRX_BWD_RES(M, N) hipLaunchKernelGGL((attn_bwd_res_kernel<M, N>), grid, blk, sm, st, a)
-    if (nkb > 1) {   // (nkb > 1 implies nkt = 8; the key-block path takes mode 0 / 1 only: stream_ok)
-      if (a.mode == 0) hipLaunchKernelGGL((attn_bwd_res_kernel<0, 8, true>), grid, blk, sm, st, a);
-      else hipLaunchKernelGGL((attn_bwd_res_kernel<1, 8, true>), grid, blk, sm, st, a);
-    } else if (a.mode == 0) { if (nkt == 2) ASRX_BWD_RES(0, 2); else if (nkt == 4) ASRX_BWD_RES(0, 4); else ASRX_BWD_RES(0, 8); }
-    else if (a.mode == 1) { if (nkt == 2) ASRX_BWD_RES(1, 2); else if (nkt == 4) ASRX_BWD_RES(1, 4); else ASRX_BWD_RES(1, 8); }
-    else { if (nkt == 2) ASRX_BWD_RES(2, 2); else if (nkt == 4) ASRX_BWD_RES(2, 4); else ASRX_BWD_RES(2, 8); }
-#undef ASRX_BWD_RES
-    ASRX_CHECK_LAUNCH();
-    if (nkb > 1) {
-      const int64_t total = (int64_t)a.B * a.Lq * a.H * d->dh;
-      const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-      hipLaunchKernelGGL(dq_finish_kernel, dim3(blocks), dim3(256), 0, st, a, d->dh, nkb);
-      ASRX_CHECK_LAUNCH();
-    }
-    return ASRX_OK;
-  }
-  rc = asrx_attn_delta(d, stream);
+  const AttnPlan pl = plan_bwd(d, a);
+  return pl.err ? pl.err : launch_bwd(a, pl, (hipStream_t)stream);
+}
+
+extern "C" int asrx_attn_kernel_name(const asrx_attn_desc* d, int32_t backward, char* buf, int32_t len) {
+  if (!buf || len < 8) return ASRX_ERR_ARG;
+  buf[0] = 0;
+  AttnArgs a;
+  int rc = fill_args(d, a);
   if (rc) return rc;
-  int nw = (a.Lk + 31) / 32;
-  if (nw > 8) nw = 8;
-  const int nblk = (a.Lk + 32 * nw - 1) / (32 * nw);
-  const int single = nblk == 1;
-  if (!single) {
-    if (!a.dq_acc) return ASRX_ERR_ARG;
-    hipMemsetAsync(a.dq_acc, 0, sizeof(float) * (size_t)a.B * a.Lq * a.H * d->dh, st);
-  }
-  const size_t smem = bwd_smem(nw, d->dh);
-  dim3 grid(nblk, a.B * a.H);
-  if (d->dh == 64) hipLaunchKernelGGL(attn_bwd_kernel<64>, grid, dim3(64 * nw), smem, st, a, nw, single);
-  else hipLaunchKernelGGL(attn_bwd_kernel<32>, grid, dim3(64 * nw), smem, st, a, nw, single);
-  ASRX_CHECK_LAUNCH();
-  if (!single) {
-    const int64_t total = (int64_t)a.B * a.Lq * a.H * d->dh;
-    unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-    hipLaunchKernelGGL(dq_finish_kernel, dim3(blocks), dim3(256), 0, st, a, d->dh, 1);
-    ASRX_CHECK_LAUNCH();
-  }
+  const AttnPlan pl = backward ? plan_bwd(d, a) : plan_fwd(d, a);
+  if (pl.err) return pl.err;
+  plan_name(pl, buf, len);
   return ASRX_OK;
 }
 

@@ -42,7 +42,8 @@ extern "C" {
  * 12: log-mel filterbank features and CMVN: asrx_logmel, asrx_logmel_pass, asrx_stft_power, asrx_cmvn,
  * asrx_feature_stats.  13: padded batches: asrx_length_mask turns lengths into the key-validity bytes of mask mode
  * 1).  14: label-smoothed cross-entropy over vocabularies up to 2^20, with fp32 or bf16 gradients and perplexity /
- * accuracy statistics: asrx_cross_entropy_ls, asrx_xent_workspace_elems). */
+ * accuracy statistics: asrx_cross_entropy_ls, asrx_xent_workspace_elems.  15: asrx_attn_kernel_name, the kernels an
+ * attention call would enqueue). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -262,6 +263,10 @@ int asrx_layernorm_fwd_attn_dropgen(const float* x, void* y, const float* gamma,
                                     float* rstd, int64_t rows, int32_t d_model, float eps, const asrx_attn_desc* d,
                                     void* stream);
 int asrx_attention_bwd(const asrx_attn_desc* d, void* stream);
+/* The kernels asrx_attention_fwd (backward == 0) or asrx_attention_bwd would enqueue for d, in order, joined by " + ",
+ * named as rocprofv3 lists them; returns the code the call itself would return. Host arithmetic only: no pointer in d is
+ * dereferenced, no device is touched. */
+int asrx_attn_kernel_name(const asrx_attn_desc* d, int32_t backward, char* buf, int32_t len);
 
 /* ---------------------------------------------------------------------------------------------------
  * Row softmax over materialised scores (the unfused path; HBM-roofline kernel of BASELINE.md §3):

@@ -42,25 +42,26 @@ D = H * DH
 NEG = P.NEG
 R_RAISE = {"tail_spike": 2048.0, "tail_pair": 2048.0}
 
-# (id, ASRX_ATTN_KERNEL, Lq, Lk, form) and the kernels the case reaches once its validity rows are word-aligned
-# (DESIGN.md §18's table; rows off a word boundary take attn_fwd_res_kernel<1> up to 256 keys, the tiled pair past it)
+# (id, ASRX_ATTN_KERNEL, Lq, Lk, form).  The kernels each case reaches once its validity rows are word-aligned are the
+# table KEYMASK of tests/test_attn_plan_table.py, asserted there through asrx_attn_kernel_name (rows off a word boundary
+# take attn_fwd_res_kernel<1, false> up to 256 keys, the tiled pair past it)
 SHAPES = [
-    ("self-249", "auto", 249, 249, "keys"),       # stream<1>, two chunks; bwd_res<1, 8>
+    ("self-249", "auto", 249, 249, "keys"),
     ("self-129", "auto", 129, 129, "keys"),
     ("self-190", "auto", 190, 190, "keys"),
     ("self-255", "auto", 255, 255, "keys"),
-    ("self-257", "auto", 257, 257, "keys"),       # stream<1>, Lk > 256; key-block bwd_res<1, 8, true>
+    ("self-257", "auto", 257, 257, "keys"),
     ("self-386", "auto", 386, 386, "keys"),
     ("self-999", "auto", 999, 999, "keys"),
-    ("cross-16x249", "auto", 16, 249, "keys"),    # res<1> (control: it reads bytes)
-    ("cross-70x249", "auto", 70, 249, "keys"),    # stream<1> via take_stream
-    ("cross-16x257", "auto", 16, 257, "keys"),    # stream<1>
+    ("cross-16x249", "auto", 16, 249, "keys"),
+    ("cross-70x249", "auto", 70, 249, "keys"),
+    ("cross-16x257", "auto", 16, 257, "keys"),
     ("cross-16x999", "auto", 16, 999, "keys"),
-    ("dec-249", "auto", 249, 249, "decoder"),     # stream<1> causal, and the masked backwards
+    ("dec-249", "auto", 249, 249, "decoder"),
     ("dec-257", "auto", 257, 257, "decoder"),
     ("dec-302", "auto", 302, 302, "decoder"),
     ("dec-303", "auto", 303, 303, "decoder"),
-    ("ctl-252", "auto", 252, 252, "keys"),        # controls: Lk % 4 == 0; the tiled and the resident kernels
+    ("ctl-252", "auto", 252, 252, "keys"),   # controls: Lk % 4 == 0; the tiled and the resident kernels
     ("ctl-tiled-259", "tiled", 259, 259, "keys"),
     ("ctl-resident-249", "resident", 249, 249, "keys"),
 ]

@@ -19,31 +19,12 @@ Profiles (log2 units; a "tile" is 32 keys, the forwards' key tile):
   shared_top    (backward) 2 - 3 keys within 1 unit hold >= 0.999 of a row, the rest >= 25 below: dS is not ~0
 Masks hide scores >= 20 above every live score of their row (exact integer codes in the leading dimensions).
 
-Forward kernels asrx_attention_fwd can launch, and the cases (B = H = 2, dh = 64 unless noted) that reach them:
-  attn_fwd_kq_kernel<false>         auto  none   (64,249) (5,17) (33,256) (64,100)   [quarter_skew: combine, empty quarters]
-  attn_fwd_kq_kernel<true>          auto  none   (64,249) dropout
-  attn_fwd_res_kernel<0>            resident none (100,200) (249,249); auto (64,100) dropout
-  attn_fwd_res_kernel<0, W8>        resident none (249,249) dropout
-  attn_fwd_res_kernel<1>            auto  decoder (70,70) (33,33); causal / key / query validity cases at 33, 70
-  attn_fwd_res_kernel<2>            auto  dense  (40,40); the dense mask cases at 40; the mask at its allocation's end
-  attn_fwd_stream_kernel<0, false>  auto  none   (57,1031) (300,300) (64,257) (100,200)
-  attn_fwd_stream_kernel<0, true>   auto  none   (57,1031) (300,300) dropout
-  attn_fwd_stream_kernel<1, false>  auto  decoder (300,300); causal / key / query validity cases at 300
-  attn_fwd_stream_kernel<1, true>   auto  decoder (300,300) dropout (the exact-rescale copy)
-  (mode 1 here has L = 300, a multiple of 4, Lq == Lk and validity rows L bytes apart.  Key-only masks with Lq != Lk,
-   key counts that are no multiple of 4 on either side of 256, validity rows at other strides and bases, and the
-   backward under a key-only mask — res<1>, stream<1, *>, bwd_res<1, 8> and <1, 8, true>, the tiled pair — are
-   tests/test_gpu_attention_keymask.py's, with this file's Ref, check_fwd, run_fwd / run_bwd and bounds)
-  attn_fwd_kernel<64>               tiled none (64,249) (300,300); dropout without keep words; auto dense (300,300)
-  attn_fwd_kernel<32>               auto  none (64,249) dh = 32
-Backward kernels asrx_attention_bwd can launch (shared_top; ramp_big at (300,300)):
-  attn_bwd_res_kernel<0, 2|4|8>     auto none (64,64) (64,100) (64,249)
-  attn_bwd_res_kernel<1, 2|4|8>     auto decoder (33,33) (70,70) (249,249)
-  attn_bwd_res_kernel<2, 2|4|8>     auto dense (40,40) (100,100) (200,200)
-  attn_bwd_res_kernel<0, 8, true>   auto none (57,1031) (300,300), with dropout keep words, with / without o_lo
-  attn_bwd_res_kernel<1, 8, true>   auto decoder (300,300), with dropout keep words
-  attn_bwd_kernel<64> (+ delta)     tiled (64,249) single block, (300,300) key blocks; dropout without keep words
-  attn_bwd_kernel<32> (+ delta)     auto (64,249) dh = 32
+Which kernels asrx_attention_fwd / asrx_attention_bwd launch for each case of FWD_CASES and BWD_CASES below (B = H = 2)
+is the table PEAKED_FWD / PEAKED_BWD of tests/test_attn_plan_table.py, asserted there on the CPU through
+asrx_attn_kernel_name together with "every instantiation is reached by some case".  Mode 1 here has L = 300, a multiple
+of 4, Lq == Lk and validity rows L bytes apart; key-only masks with Lq != Lk, key counts that are no multiple of 4 on
+either side of 256, validity rows at other strides and bases, and the backward under a key-only mask are
+tests/test_gpu_attention_keymask.py's, with this file's Ref, check_fwd, run_fwd / run_bwd and bounds.
 
 Bounds: per (b, h, q) max_d |O - ref| <= 1e-2 max |V(b, h)| (the project's forward bound, per row and head);
 |lse - log2 sum 2^s| <= 1e-3 on live rows, lse = +inf and an exactly zero output on fully masked rows; per (b, h)
@@ -471,7 +452,7 @@ def run_bwd(run, ref, dh, dOb, keep_words=True):
 PROFILES = ["ramp_small", "ramp_big", "threshold", "descending", "last_key", "row_spike", "all_negative",
             "quarter_skew"]
 
-# (id, ASRX_ATTN_KERNEL, Lq, Lk, dh, mask, dropout, keep words) -> kernel: the module docstring's table
+# (id, ASRX_ATTN_KERNEL, Lq, Lk, dh, mask, dropout, keep words) -> kernel: test_attn_plan_table.PEAKED_FWD
 FWD_CASES = [
     ("kq-64x249", "auto", 64, 249, 64, "none", False, True),
     ("kq-5x17", "auto", 5, 17, 64, "none", False, True),
