@@ -91,6 +91,9 @@ SPECAUG_RUN = CONSTS["ASRX_SPECAUG_RUN"]            # frames one workgroup of as
 LOGMEL_MAX_MELS = CONSTS["ASRX_LOGMEL_MAX_MELS"]
 MAX_ROWSUM_GROUPS = 64      # norm.hip RG_MAX
 CTC_MAX_TARGET = 255        # longest target asrx_ctc_loss takes (511 extended states)
+CTC_LONG_MAX_TARGET = CONSTS["ASRX_CTC_LONG_MAX_TARGET"]   # ... asrx_ctc_loss_long / asrx_ctc_align_long take
+ED_MAX_TOKENS = 255         # longest kept sequence asrx_edit_distance takes
+ED_LONG_MAX_TOKENS = CONSTS["ASRX_ED_LONG_MAX_TOKENS"]     # ... asrx_edit_distance_long takes
 
 ERRORS = {CONSTS["ASRX_ERR_ARG"]: "bad argument", CONSTS["ASRX_ERR_LAUNCH"]: "launch failure",
           CONSTS["ASRX_ERR_UNSUPPORTED"]: "unsupported shape/layout"}

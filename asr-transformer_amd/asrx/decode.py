@@ -468,9 +468,11 @@ def transformer_align(model, spectrum, text, mask=None, input_lengths=None, *, b
         mask = torch.ones_like(text) if dec.pad_token_id is None else text != int(dec.pad_token_id)
     targets, lengths = K.ctc_targets(text if text.stride(1) == 1 else text.contiguous(),
                                      mask.to(device=dev, dtype=torch.float32).contiguous(), drop, model.ctc_blank)
-    # (a row longer than the kernel's 255 labels has no alignment there: its score is -inf)
+    # The Trainer's width rule (a text row holds BOS and EOS): up to 257 columns take asrx_ctc_align (255 labels),
+    # wider rows asrx_ctc_align_long (4095).  A row with more labels than that has no alignment: its score is -inf.
+    use_long, max_l = K.ctc_path(targets.shape[1], framing=2)
     return K.ctc_align(logits, model.ctc_head.V, T, targets, lengths, _i32_on(dev, input_lengths),
-                       max_target_len=min(targets.shape[1], 255), blank=model.ctc_blank)
+                       max_target_len=max_l, blank=model.ctc_blank, long=use_long)
 
 
 # ------------------------------------------------------------------------------------------- two-pass decoding

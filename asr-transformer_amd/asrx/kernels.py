@@ -7,7 +7,8 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from ._lib import (BF16, BITS, CONSTS, CTC_MAX_TARGET, CTC_MEAN, CTC_SUM, ED_CROSS, ED_GROUP, ED_PAIRS, F32,
+from ._lib import (BF16, BITS, CONSTS, CTC_LONG_MAX_TARGET, CTC_MAX_TARGET, CTC_MEAN, CTC_SUM, ED_CROSS, ED_GROUP,
+                   ED_LONG_MAX_TOKENS, ED_MAX_TOKENS, ED_PAIRS, F32,
                    MAX_ROWSUM_GROUPS, AttnDesc, GemmDesc, GemmGroupDev, RowsumGroup, call)
 
 _U64 = (1 << 64) - 1
@@ -1260,10 +1261,33 @@ def cross_entropy(logits, V, target, ignore_index=-100, grad_scale=1.0, want_gra
 CTC_REDUCTIONS = {"sum": CTC_SUM, "mean": CTC_MEAN}
 
 
-def ctc_workspace_elems(B, T, max_target_len):
-    """fp32 workspace elements of ctc_loss (asrx_ctc_workspace_elems: the C-ABI's own size rule)."""
+def ctc_path(width, framing=0):
+    """Which CTC entry a row width takes, decided on the host: (use_long, max_target_len).  `width` columns of which
+    `framing` hold no label (2 for a teacher-forced text row: BOS and EOS) bound the labels by width - framing: up to
+    255 of them take the one-wave kernels (asrx_ctc_loss / asrx_ctc_align) with max_target_len = min(width, 255), more
+    take the `_long` entries with min(width, 4095).  Targets longer than the returned bound have no alignment."""
+    use_long = width - framing > CTC_MAX_TARGET
+    return use_long, min(width, CTC_LONG_MAX_TARGET if use_long else CTC_MAX_TARGET)
+
+
+def edit_path(*cols):
+    """Whether row widths take asrx_edit_distance_long, and the token bound scored with: (use_long, max_tokens)."""
+    use_long = max(cols) > ED_MAX_TOKENS
+    return use_long, ED_LONG_MAX_TOKENS if use_long else ED_MAX_TOKENS
+
+
+def _long_size(fn, B, T, max_target_len):   # the `_long` size helpers write an int64 count (-1: refused)
+    n = ctypes.c_int64(0)
+    fn(B, T, max_target_len, ctypes.byref(n))
+    return n.value
+
+
+def ctc_workspace_elems(B, T, max_target_len, long=False):
+    """fp32 workspace elements of ctc_loss (asrx_ctc_workspace_elems, long: asrx_ctc_long_workspace_elems: the C-ABI's
+    own size rule)."""
     from ._lib import lib
-    n = lib().asrx_ctc_workspace_elems(B, T, max_target_len)
+    n = _long_size(lib().asrx_ctc_long_workspace_elems, B, T, max_target_len) if long else \
+        lib().asrx_ctc_workspace_elems(B, T, max_target_len)
     if n < 0:
         raise RuntimeError(f"asrx: no CTC workspace for B {B}, T {T}, max target length {max_target_len}")
     return n
@@ -1271,10 +1295,11 @@ def ctc_workspace_elems(B, T, max_target_len):
 
 def ctc_loss(logits, V, T, targets, target_lengths, input_lengths=None, max_target_len=None, blank=0,
              reduction="mean", zero_infinity=False, grad_scale=1.0, grad_dtype=torch.bfloat16, want_grad=True,
-             loss_add=None, loss_add_scale=1.0, loss_scale=1.0):
+             loss_add=None, loss_add_scale=1.0, loss_scale=1.0, long=False):
     """CTC on logits fp32 [B*T, ld] (rows b*T + t, contiguous rows; asrx_ctc_loss, log-softmax fused): targets int64
     [B, >= max_target_len], target_lengths / input_lengths int32 [B] (input_lengths None = T).  max_target_len is the
-    host-side bound of the lengths (default: the targets' width).  Returns (loss[1] = loss_add_scale * loss_add +
+    host-side bound of the lengths (default: the targets' width), at most 255, or 4095 with long=True
+    (asrx_ctc_loss_long: a workgroup per sample; see ctc_path).  Returns (loss[1] = loss_add_scale * loss_add +
     loss_scale * reduction, nll fp32 [B], dlogits [B*T, ld] in grad_dtype or None)."""
     _cuda(logits, targets, target_lengths, input_lengths, loss_add)
     rows, ld = logits.shape
@@ -1286,9 +1311,10 @@ def ctc_loss(logits, V, T, targets, target_lengths, input_lengths=None, max_targ
     nll = torch.empty(B, device=dev, dtype=torch.float32)
     dl = torch.empty(rows, ld, device=dev, dtype=grad_dtype) if want_grad else None
     # (the size rule refuses what the call refuses: let the call report a too long target)
-    n = ctc_workspace_elems(B, T, min(max(max_target_len, 0), CTC_MAX_TARGET))
+    n = ctc_workspace_elems(B, T, min(max(max_target_len, 0), CTC_LONG_MAX_TARGET if long else CTC_MAX_TARGET), long)
     ws = torch.empty(n, device=dev, dtype=torch.float32)
-    call("asrx_ctc_loss", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride, _p(input_lengths),
+    call("asrx_ctc_loss_long" if long else "asrx_ctc_loss", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride,
+         _p(input_lengths),
          target_lengths.data_ptr(), max_target_len, blank, CTC_REDUCTIONS[reduction], int(zero_infinity), grad_scale,
          nll.data_ptr(), loss.data_ptr(), _p(dl), code(dl) if dl is not None else 0, _p(loss_add),
          loss_add_scale, loss_scale, ws.data_ptr(), n, stream())
@@ -1359,19 +1385,22 @@ class CtcAlignment(NamedTuple):
     target_lengths: Optional[torch.Tensor] = None
 
 
-def ctc_align_workspace_words(B, T, max_target_len):
-    """4-byte workspace words of ctc_align (asrx_ctc_align_workspace_words: the C-ABI's own size rule)."""
+def ctc_align_workspace_words(B, T, max_target_len, long=False):
+    """4-byte workspace words of ctc_align (asrx_ctc_align_workspace_words, long: asrx_ctc_align_long_workspace_words:
+    the C-ABI's own size rule)."""
     from ._lib import lib
-    n = lib().asrx_ctc_align_workspace_words(B, T, max_target_len)
+    n = _long_size(lib().asrx_ctc_align_long_workspace_words, B, T, max_target_len) if long else \
+        lib().asrx_ctc_align_workspace_words(B, T, max_target_len)
     if n < 0:
         raise RuntimeError(f"asrx: no alignment workspace for B {B}, T {T}, max target length {max_target_len}")
     return n
 
 
-def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_target_len=None, blank=0):
+def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_target_len=None, blank=0, long=False):
     """Best CTC path of logits fp32 [B*T, ld] (rows b*T + t; asrx_ctc_align, log-softmax fused) that collapses to
     targets int64 [B, >= max_target_len] of target_lengths int32 [B]; frames t >= input_lengths[b] (int32 [B], None =
-    T) are ignored.  max_target_len is the host-side bound of the lengths (default: the targets' width, at most 255).
+    T) are ignored.  max_target_len is the host-side bound of the lengths (default: the targets' width, at most 255,
+    or 4095 with long=True: asrx_ctc_align_long, a workgroup per sample; see ctc_path).
     Returns a CtcAlignment; nothing leaves the device."""
     _cuda(logits, targets, target_lengths, input_lengths)
     ld = logits.shape[1]
@@ -1380,7 +1409,7 @@ def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_tar
     dev = logits.device
     lmax = max(max_target_len, 0)
     # (the size rule refuses what the call refuses: let the call report a too long target)
-    words = ctc_align_workspace_words(B, T, min(lmax, CTC_MAX_TARGET))
+    words = ctc_align_workspace_words(B, T, min(lmax, CTC_LONG_MAX_TARGET if long else CTC_MAX_TARGET), long)
     ws = torch.empty(words, dtype=torch.int32, device=dev)
     frame_pos = torch.empty(B, T, dtype=torch.int32, device=dev)
     frame_logp = torch.empty(B, T, dtype=torch.float32, device=dev)
@@ -1388,7 +1417,8 @@ def ctc_align(logits, V, T, targets, target_lengths, input_lengths=None, max_tar
     end = torch.empty(B, lmax, dtype=torch.int32, device=dev)
     conf = torch.empty(B, lmax, dtype=torch.float32, device=dev)
     score = torch.empty(B, dtype=torch.float32, device=dev)
-    call("asrx_ctc_align", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride, _p(input_lengths),
+    call("asrx_ctc_align_long" if long else "asrx_ctc_align", logits.data_ptr(), B, T, V, ld, tgt_ptr, tgt_stride,
+         _p(input_lengths),
          target_lengths.data_ptr(), max_target_len, blank, ws.data_ptr(), words, frame_pos.data_ptr(),
          frame_logp.data_ptr(), start.data_ptr() if lmax else None, end.data_ptr() if lmax else None,
          conf.data_ptr() if lmax else None, score.data_ptr(), stream())
@@ -1477,8 +1507,10 @@ def _rows(t, name):
 
 
 def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, drop=(), stop=None, mode="pairs", W=1,
-                  n_hyp=None, counts=True, out=None):
-    """Levenshtein alignment of token rows (asrx_edit_distance).  hyp int64 [R, cols] (any row stride), ref int64
+                  n_hyp=None, counts=True, out=None, long=False):
+    """Levenshtein alignment of token rows (asrx_edit_distance: sequences of up to 255 kept tokens, dist -2 beyond;
+    long=True: asrx_edit_distance_long, up to 4095, the same integers; see edit_path).  hyp int64 [R, cols] (any row
+    stride), ref int64
     [R', cols'] (None in "cross" mode), lengths int32 per row or None (= cols).  A row's sequence: its first `length`
     entries, cut before the first `stop` id (None: no stop), without the (at most four) `drop` ids.  "pairs": R' = R
     pairs; "group": row n against ref row n // W; "cross": R // W groups, all W x W pairs of each.  n_hyp int32 per
@@ -1511,7 +1543,8 @@ def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, drop=(), st
         assert dist.dtype == torch.int32 and dist.numel() == N and dist.is_contiguous()
         assert cnt is None or (cnt.dtype == torch.int32 and cnt.numel() == 4 * N and cnt.is_contiguous())
     cross = mode == "cross"
-    call("asrx_edit_distance", hyp.data_ptr(), hyp.stride(0), hyp.shape[1], _p(hyp_lengths),
+    call("asrx_edit_distance_long" if long else "asrx_edit_distance", hyp.data_ptr(), hyp.stride(0), hyp.shape[1],
+         _p(hyp_lengths),
          None if cross else ref.data_ptr(), 0 if cross else ref.stride(0), 0 if cross else ref.shape[1],
          None if cross else _p(ref_lengths), N, code, W, None if mode == "pairs" else _p(n_hyp), *_drop_ids(drop),
          -1 if stop is None else int(stop), dist.data_ptr(), _p(cnt), stream())

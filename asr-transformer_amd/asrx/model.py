@@ -303,7 +303,8 @@ class Transformer(nn.Module):
 
     def align(self, spectrum, text, mask=None, input_lengths=None):
         """Forced alignment without the decoder (ctc=True models): the best CTC path through the T' encoder frames
-        that collapses to the transcript, on the device (asrx_ctc_align).  text: (B, n) token ids, of which the
+        that collapses to the transcript, on the device (asrx_ctc_align; asrx_ctc_align_long for n > 257, up to 4095
+        labels).  text: (B, n) token ids, of which the
         positions with mask >= 1 (None: text != pad) that are not BOS / EOS / PAD are the labels, as in training;
         input_lengths: (B,) valid encoder frames (None: all T').  Returns a CtcAlignment, all on the device:
         frame_pos (B, T') int32 label position per frame (-1: blank), frame_logp (B, T') fp32, start / end (B, Lmax)

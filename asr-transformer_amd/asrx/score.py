@@ -15,8 +15,9 @@ from .decode import BeamResult, RescoreResult, check_mbr_scale
 
 class EditCounts(NamedTuple):
     """edit_distance: int32 device tensors of one shape ((N,) "pairs", (B, W) "group", (B, W, W) "cross").  dist =
-    sub + dele + ins; -1 marks a pair with an absent slot, -2 a sequence of more than 255 tokens (the counts are -1
-    there).  dele: reference tokens without a hypothesis counterpart; ins: the converse; ref_len: reference tokens."""
+    sub + dele + ins; -1 marks a pair with an absent slot, -2 a sequence of more than 4095 tokens (255 where no row
+    has more than 255 columns; the counts are -1 there).  dele: reference tokens without a hypothesis counterpart; ins:
+    the converse; ref_len: reference tokens."""
     dist: torch.Tensor
     sub: torch.Tensor
     dele: torch.Tensor
@@ -53,7 +54,8 @@ def _i32(t, dev):
 @torch.no_grad()
 def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, *, drop=(), stop=None, mode="pairs",
                   n_hyp=None):
-    """Levenshtein alignment of token rows on the device (one asrx_edit_distance launch, no synchronisation).
+    """Levenshtein alignment of token rows on the device (one asrx_edit_distance launch, or asrx_edit_distance_long
+    where a side has more than 255 columns: the same integers; no synchronisation).
 
     mode "pairs": hyp (N, cols) against ref (N, cols'), row by row.  "group": hyp (B, W, cols), each of a sample's W
     hypotheses against its one reference, ref (B, cols').  "cross": hyp (B, W, cols), all W x W pairs within each
@@ -83,14 +85,16 @@ def edit_distance(hyp, ref=None, hyp_lengths=None, ref_lengths=None, *, drop=(),
     dev = _device(hyp, ref)
     hyp = _rows(hyp, dev).reshape(-1, hyp.shape[-1])
     ref = None if mode == "cross" else _rows(ref, dev)
+    use_long, _ = K.edit_path(hyp.shape[1], 0 if ref is None else ref.shape[1])
     dist, cnt = K.edit_distance(hyp, ref, _i32(hyp_lengths, dev), None if ref is None else _i32(ref_lengths, dev),
-                                drop, stop, mode, W, None if mode == "pairs" else _i32(n_hyp, dev))
+                                drop, stop, mode, W, None if mode == "pairs" else _i32(n_hyp, dev), long=use_long)
     return EditCounts(dist.view(shape), *(cnt[:, k].view(shape) for k in range(4)))
 
 
-def reduce_counts(records):
+def reduce_counts(records, max_tokens=255):
     """The arithmetic of ErrorRate.compute on host data: records = [(dist [B, W], counts [B, W, 4]), ...] integer
-    tensors as asrx_edit_distance writes them in GROUP mode (slot 0 the 1-best)."""
+    tensors as asrx_edit_distance writes them in GROUP mode (slot 0 the 1-best).  max_tokens: the bound the records
+    were scored with (one int, or one per record), named where a dist of -2 is met."""
     tot = dict(edits=0, sub=0, dele=0, ins=0, ref=0, samples=0, wrong=0, oracle=0)
     nbest = False
     base = 0
@@ -101,8 +105,9 @@ def reduce_counts(records):
         long = (dist == -2).nonzero()
         if len(long):
             b, w = (int(x) for x in long[0])
-            raise ValueError(f"sample {base + b} (row {b} of update {u}, hypothesis {w}): a sequence of more than 255 "
-                             f"tokens cannot be scored")
+            bound = max_tokens[u] if isinstance(max_tokens, (list, tuple)) else max_tokens
+            raise ValueError(f"sample {base + b} (row {b} of update {u}, hypothesis {w}): a sequence of more than "
+                             f"{bound} tokens cannot be scored")
         none = (dist[:, 0] < 0).nonzero()
         if len(none):
             b = int(none[0])
@@ -148,9 +153,11 @@ class ErrorRate:
             raise ValueError(f"at most four drop ids, got {len(self.drop)}")
         self.stop = None if stop is None else int(stop)
         self._records = []
+        self._bounds = []     # per update: the token bound it was scored with (255, or 4095 for wide rows)
 
     def reset(self):
         self._records = []
+        self._bounds = []
 
     @torch.no_grad()
     def update(self, hyp, ref, hyp_lengths=None, ref_lengths=None, n_hyp=None):
@@ -164,9 +171,11 @@ class ErrorRate:
         dev = _device(hyp, ref)
         B, W, cols = hyp.shape
         hyp = _rows(hyp, dev).reshape(B * W, cols)
+        use_long, bound = K.edit_path(cols, ref.shape[1])
         dist, cnt = K.edit_distance(hyp, _rows(ref, dev), _i32(hyp_lengths, dev), _i32(ref_lengths, dev), self.drop,
-                                    self.stop, "group", W, _i32(n_hyp, dev))
+                                    self.stop, "group", W, _i32(n_hyp, dev), long=use_long)
         self._records.append((dist, cnt, B, W))
+        self._bounds.append(bound)
 
     def update_result(self, result, text):
         """result: a BeamResult / RescoreResult of any decoder (slots with a non-finite score are absent; they come
@@ -187,7 +196,7 @@ class ErrorRate:
         for _, _, B, W in self._records:
             host.append((flat[o:o + B * W].view(B, W), flat[o + B * W:o + 5 * B * W].view(B, W, 4)))
             o += 5 * B * W
-        return reduce_counts(host)
+        return reduce_counts(host, max_tokens=list(self._bounds))
 
 
 @torch.no_grad()
@@ -207,7 +216,7 @@ def mbr_rerank(result, scale=1.0, drop=(), stop=None):
     sc = scores.to(device=dev, dtype=torch.float32).contiguous()
     n_hyp = torch.isfinite(sc).sum(dim=1).to(torch.int32)
     dist, _ = K.edit_distance(_rows(tokens, dev).reshape(B * W, cols), None, None, None, drop, stop, "cross", W, n_hyp,
-                              counts=False)
+                              counts=False, long=K.edit_path(cols)[0])
     risk, order = K.mbr_rank(dist, sc.reshape(-1), B, W, scale, n_hyp)
     flat = torch.cat([risk.view(torch.int32).reshape(-1), order.reshape(-1)]).cpu()
     risk = flat[:B * W].view(torch.float32).view(B, W)

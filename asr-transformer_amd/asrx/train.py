@@ -446,11 +446,14 @@ class Trainer:
                                              model.ctc_blank)
             cl = S["ctc_logits"]
             Tp = cl.shape[0] // text.shape[0]
-            # (a row longer than the kernel's 255 labels has no alignment there: zero_infinity drops it)
+            # A text row holds BOS and EOS beside its labels: up to 257 columns take asrx_ctc_loss (at most 255
+            # labels), wider rows asrx_ctc_loss_long (at most 4095), eager and captured alike.  A row with more
+            # labels than that bound has no alignment there: zero_infinity drops it from the CTC term.
+            use_long, max_l = K.ctc_path(ctc_tgt.shape[1], framing=2)
             loss, _, dctc = K.ctc_loss(cl, model.ctc_head.V, Tp, ctc_tgt, ctc_len, input_lengths=enc_len,
-                                       max_target_len=min(ctc_tgt.shape[1], 255), blank=model.ctc_blank,
+                                       max_target_len=max_l, blank=model.ctc_blank,
                                        reduction="mean", zero_infinity=True, grad_scale=lam, grad_dtype=C.cd,
-                                       loss_add=loss, loss_add_scale=1.0 - lam, loss_scale=lam)
+                                       loss_add=loss, loss_add_scale=1.0 - lam, loss_scale=lam, long=use_long)
         if self._wonly and C.cd == torch.bfloat16 and all(p.grad is not None for p in self.store.params):
             K.zero_spans(self.store.grad, self._zero_spans)
             C.fresh = FreshGrads(self.store, self._wonly)

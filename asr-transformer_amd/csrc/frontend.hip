@@ -1147,7 +1147,7 @@ inline unsigned grid_for(int64_t work, int cap = 8192) {
 
 ASRX_SEED_OFFSET_SETTER(frontend)
 
-extern "C" int asrx_version(void) { return 15; }
+extern "C" int asrx_version(void) { return 16; }
 
 extern "C" int asrx_struct_sizes(int64_t* out, int32_t n) {
   if (!out || n < 0) return ASRX_ERR_ARG;

@@ -43,7 +43,8 @@ extern "C" {
  * asrx_feature_stats.  13: padded batches: asrx_length_mask turns lengths into the key-validity bytes of mask mode
  * 1).  14: label-smoothed cross-entropy over vocabularies up to 2^20, with fp32 or bf16 gradients and perplexity /
  * accuracy statistics: asrx_cross_entropy_ls, asrx_xent_workspace_elems.  15: asrx_attn_kernel_name, the kernels an
- * attention call would enqueue). */
+ * attention call would enqueue).  16: transcripts beyond 255 labels: asrx_ctc_loss_long, asrx_ctc_long_workspace_elems,
+ * asrx_ctc_align_long, asrx_ctc_align_long_workspace_words, asrx_edit_distance_long). */
 int asrx_version(void);
 
 /* sizeof of the descriptor structs as this library was compiled (binding check: a ctypes / cgo mirror of a
@@ -510,6 +511,28 @@ int asrx_ctc_loss(const float* logits, int32_t B, int32_t T, int32_t V, int64_t 
                   float* nll, float* loss, void* dlogits, int32_t dlogits_dtype, const float* loss_add,
                   float loss_add_scale, float loss_scale, float* ws, int64_t ws_elems, void* stream);
 
+/* CTC beyond 255 labels (version >= 16): asrx_ctc_loss for 0 <= max_target_len <= ASRX_CTC_LONG_MAX_TARGET.  Same
+ * parameter list, semantics, reductions, outputs and argument checks (in the same order, before any device access) as
+ * asrx_ctc_loss; only the bound differs: max_target_len > 4095 returns ASRX_ERR_UNSUPPORTED and the size helper -1.
+ * One workgroup of NW = ceil((max_target_len + 1) / 256) wave64s per (sample, direction), lane i of the workgroup
+ * owning the (blank, label) pairs 4i .. 4i + 3; the neighbour value crosses a wave seam through LDS slots
+ * double-buffered by frame parity, one workgroup barrier per frame.  The workspace holds the row statistics, 4100 ints
+ * per sample (rank | count << 16 per label, the lengths), and log2 alpha / beta rows of 512 * NW floats.
+ * asrx_ctc_long_workspace_elems writes that number of fp32 elements to *elems and returns ASRX_OK; on bad arguments
+ * (B, T <= 0, max_target_len outside [0, 4095], a NULL elems) it returns -1 (ASRX_ERR_ARG) and writes -1.  The count is
+ * an int64 (more than 2^31 elements at B 64, T 4000, L 4095), hence the pointer: the result type stays every entry's
+ * int.  Host-only arithmetic.  The short range is accepted too (NW = 1); results agree with asrx_ctc_loss within
+ * rounding, not in bits.  Deterministic, no atomics, no allocation, no synchronisation, four launches,
+ * graph-capturable.  ld <= 8192, B <= 65535. */
+#define ASRX_CTC_LONG_MAX_TARGET 4095
+int asrx_ctc_long_workspace_elems(int32_t B, int32_t T, int32_t max_target_len, int64_t* elems);
+int asrx_ctc_loss_long(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int64_t* targets,
+                       int64_t tgt_stride, const int32_t* input_lengths, const int32_t* target_lengths,
+                       int32_t max_target_len, int32_t blank, int32_t reduction, int32_t zero_infinity,
+                       float grad_scale, float* nll, float* loss, void* dlogits, int32_t dlogits_dtype,
+                       const float* loss_add, float loss_add_scale, float loss_scale, float* ws, int64_t ws_elems,
+                       void* stream);
+
 /* CTC targets of a teacher-forced batch: text int64 [B][n] (row stride ld_text; n = L + 1 columns of the step's token
  * rows) and the float pad mask [B][n] (row stride ld_mask).  Per sample, in order, the tokens at positions with
  * mask >= 1 that are none of drop[0 .. ndrop) (HOST array, ndrop <= 4: BOS, EOS, PAD / blank) go left-packed to
@@ -659,6 +682,21 @@ int asrx_ctc_align(const float* logits, int32_t B, int32_t T, int32_t V, int64_t
                    float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score,
                    void* stream);
 
+/* Forced alignment beyond 255 labels (version >= 16): asrx_ctc_align for 0 <= max_target_len <=
+ * ASRX_CTC_LONG_MAX_TARGET, with the same parameter list, outputs, tie rule, "no alignment" conventions and argument
+ * checks; max_target_len > 4095 returns ASRX_ERR_UNSUPPORTED and the size helper -1.  One workgroup of NW =
+ * ceil((max_target_len + 1) / 256) wave64s per sample (the layout of asrx_ctc_loss_long); the renormalising maximum is
+ * a workgroup maximum; the backpointers, one 16-bit word per lane and frame, [frame][64 * NW], always live in the
+ * workspace: asrx_ctc_align_long_workspace_words writes 2 * B * T + 32 * NW * B * T (4-byte words, an int64) to *words
+ * by asrx_ctc_long_workspace_elems's convention.  The backtrace is a plain dependent walk over the backpointer words.
+ * Deterministic, no allocation, no synchronisation, two launches. */
+int asrx_ctc_align_long_workspace_words(int32_t B, int32_t T, int32_t max_target_len, int64_t* words);
+int asrx_ctc_align_long(const float* logits, int32_t B, int32_t T, int32_t V, int64_t ld, const int64_t* targets,
+                        int64_t tgt_stride, const int32_t* input_lengths, const int32_t* target_lengths,
+                        int32_t max_target_len, int32_t blank, void* ws, int64_t ws_words, int32_t* frame_pos,
+                        float* frame_logp, int32_t* tok_start, int32_t* tok_end, float* tok_conf, float* score,
+                        void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * Edit distance and minimum-Bayes-risk ranking (version >= 9): how many errors a decoder's output holds against a
  * transcript, and which hypothesis of an n-best list has the smallest expected distance to the others.
@@ -690,6 +728,16 @@ int asrx_edit_distance(const int64_t* hyp, int64_t ld_hyp, int32_t hyp_cols, con
                        const int64_t* ref, int64_t ld_ref, int32_t ref_cols, const int32_t* ref_len, int32_t N,
                        int32_t mode, int32_t W, const int32_t* n_hyp, const int64_t* drop, int32_t ndrop,
                        int64_t stop_id, int32_t* dist, int32_t* counts, void* stream);
+/* asrx_edit_distance for sequences of up to ASRX_ED_LONG_MAX_TOKENS kept tokens (version >= 16): the same parameter
+ * list, modes, filtering, argument checks, -1 convention and lexicographic (edits, substitutions) optimum; dist -2
+ * marks a sequence of more than 4095 tokens.  The same wavefront, one pair (one wave64) per workgroup with both rows
+ * and the column boundary in 80 KiB of dynamic LDS, the cost packed as edits << 13 | substitutions.  On inputs
+ * asrx_edit_distance accepts, the integers are identical. */
+#define ASRX_ED_LONG_MAX_TOKENS 4095
+int asrx_edit_distance_long(const int64_t* hyp, int64_t ld_hyp, int32_t hyp_cols, const int32_t* hyp_len,
+                            const int64_t* ref, int64_t ld_ref, int32_t ref_cols, const int32_t* ref_len, int32_t N,
+                            int32_t mode, int32_t W, const int32_t* n_hyp, const int64_t* drop, int32_t ndrop,
+                            int64_t stop_id, int32_t* dist, int32_t* counts, void* stream);
 /* Minimum-Bayes-risk ranking of B n-best lists from their pairwise distances (asrx_edit_distance in CROSS mode):
  * dist int32 [B][W][W], score fp32 [B][W], n_hyp int32 [B] or NULL.  Slot j is live if j < n_hyp[b], its score is
  * finite and dist[b][j][j] >= 0 (an absent or unsupported hypothesis is dead).  With p_j = exp(scale * (s_j - max live
